@@ -10,6 +10,13 @@ each payload byte is both encoded and decoded inside one step.
 Multi-GPU (torchrun, one process per GPU): blocks are partitioned, each rank owns its own
 2^20 blocks (fbn offset by rank), there is no data-path collective (a FEC block never spans
 GPUs); barrier + max-over-ranks timing only.  scaling = weak.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline figure needs and no
+more: set-up, W warm-up steps, N timed steps, the outputs of the last step to --dump-outputs DIR when
+given, and the JSON line (the step's own kernels, timed by events inside the timed steps, are in it).
+--full adds everything else: the CPU baseline (the reference's pluglets on the host cores), the byte
+gates on the timed step's outputs, and the side legs (other shapes, repair frames, windows, XOR, PCIe,
+the batching adapter and the synchronous hooks); --no-cpu, --no-legs and --no-pcie trim a --full run.
 """
 from __future__ import annotations
 
@@ -59,9 +66,19 @@ def parse():
     p.add_argument("--dry-run", action="store_true",
                    help="launcher / rendezvous check without a GPU: ranks time an empty step on gloo; "
                         "value is 0 and the line says dry_run (tests only)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline figure as well: the CPU baseline, the byte gates on the "
+                        "timed outputs, the side legs (other shapes, frames, windows, XOR, PCIe, batching, hooks); "
+                        "--no-cpu, --no-legs and --no-pcie trim it.  A plain run sets up, warms up, times the "
+                        "steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32; "
+                        "a fixed seeded sample of the blocks, at most 64 MB in all)")
     a = p.parse_args()
     if a.gpus is None:  # torchrun --nproc-per-node N bench.py: N ranks
         a.gpus = int(os.environ.get("WORLD_SIZE", "1"))
+    if not a.full:  # a plain run measures the headline figure only
+        a.no_cpu = a.no_legs = True
     return a
 
 
@@ -121,6 +138,41 @@ def check_recovered(torch, dst, src, ok, miss, nb, k, L, what):
         rows = (b.unsqueeze(1) * k + miss[c0:c1]).reshape(-1)[okc]
         drows = (b.unsqueeze(1) * em + torch.arange(e, device=src.device)).reshape(-1)[okc]
         assert bool((dst.view(nb * em, L)[drows] == src.view(nb * k, L)[rows]).all()), what
+
+
+DUMP_ROW_BYTES = 48 << 20    # --dump-outputs: the sampled symbol rows, as float32
+DUMP_STATUS_BLOCKS = 1 << 21  # the per-block status in full up to here (8 MB as float32), else sampled
+
+
+def dump_outputs(torch, out_dir, suffix, m, rep, rec_rows=None, status=None, recovered=None):
+    """--dump-outputs: what a caller of the timed step receives, from the buffers the last timed step
+    left, as out_dir/<name><suffix>.npy in float32 (bytes and bits are exact in it).  The symbol rows are
+    those of a fixed sample of the m blocks of the step's last pass (seeded, ascending; the same blocks
+    on every run with the same arguments), sized so that everything written stays below 64 MB:
+      sample_blocks   [n]            the sampled block indices (float64)
+      repairs         [n, r, L]      the encode's repair symbols
+      recovered_rows  [n, em, L]     the decode's recovered symbols, packed per block
+      recovered_mask  [n, 128]       the decode's recovered-source bits
+      status          [m] or [n]     the decode's per-block status (every block up to 2^21 blocks)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    per_block = rep[0].numel() + (rec_rows[0].numel() if rec_rows is not None else 0)
+    n = min(m, 1024, DUMP_ROW_BYTES // 4 // per_block)
+    assert n >= 1, f"--dump-outputs: one block's rows ({per_block} bytes) exceed the sample budget"
+    g = torch.Generator(device="cpu").manual_seed(0xD0C5)
+    idx = torch.randperm(m, generator=g)[:n].sort().values
+    didx = idx.to(rep.device)
+    out = {"sample_blocks": idx.numpy().astype(np.float64),
+           "repairs": rep[didx].cpu().numpy().astype(np.float32)}
+    if rec_rows is not None:
+        out["recovered_rows"] = rec_rows[didx].cpu().numpy().astype(np.float32)
+        bits = (recovered[didx].cpu().unsqueeze(-1) >> torch.arange(64, dtype=torch.int64)) & 1
+        out["recovered_mask"] = bits.reshape(n, 128).numpy().astype(np.float32)
+        st = status[:m] if m <= DUMP_STATUS_BLOCKS else status[didx]
+        out["status"] = st.cpu().numpy().astype(np.float32)
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def encode_kernel_name(k, r, L):
@@ -879,7 +931,7 @@ def main():
         """correctness gate on the benchmarked data: every recovered block's erased rows equal the originals"""
         nonlocal n_rec, n_ub
         ok = status == 0
-        if passes == 1:
+        if passes == 1 and args.full:  # a plain run counts the recovered blocks (the roofline's bytes) only
             check_recovered(torch, rec_rows, src, ok, miss, nb, k, L, "decode did not restore the sources")
         n_rec = int(ok.sum())
         n_ub = int((status == 2).sum())
@@ -943,9 +995,16 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if args.dump_outputs and args.steps + args.warmup > 0:  # before the encode gate re-codes earlier passes
+        m_last = share - (passes - 1) * nb  # the blocks of the step's last pass: what the buffers hold now
+        suffix = f"_rank{rank}" if world > 1 else ""
+        if e:
+            dump_outputs(torch, args.dump_outputs, suffix, m_last, rep, rec_rows, status, recovered)
+        else:
+            dump_outputs(torch, args.dump_outputs, suffix, m_last, rep)
     if e and not gate_first and args.steps + args.warmup > 0:
         gate()
-    if not e and args.steps + args.warmup > 0:
+    if not e and args.full and args.steps + args.warmup > 0:
         encode_gate()
     # first pass of a step: encode, apply (includes the zero/undetermined rule), plan (its own stream)
     enc_ms, apply_ms = (sum(ev[i].elapsed_time(ev[i + 1]) for ev in evs) / args.steps for i in (0, 2))
@@ -1093,7 +1152,7 @@ def main():
         if e:
             conf["decode_output"] = ("recovered symbols into new rows, packed per block (as fec_recover "
                                      "allocates each recovered symbol anew)")
-        if not e:
+        if not e and args.full:
             conf["encode_gate"] = {"passes_checked": passes, "blocks_decoded_back": n_enc_checked,
                                    "method": "per pass, sampled blocks lose min(k, r) sources and decode back "
                                              "from the pass's repairs at independently stated block numbers"}

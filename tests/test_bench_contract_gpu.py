@@ -43,7 +43,7 @@ def _check_common(d, steps, warmup, scaling="weak"):
 
 @pytest.mark.gpu
 def test_bench_line_default_workload():
-    d = _run(["--steps", "2", "--warmup", "1", "--no-legs", "--cpu-seconds", "1", "--cpu-blocks", "256"])
+    d = _run(["--full", "--steps", "2", "--warmup", "1", "--no-legs", "--cpu-seconds", "1", "--cpu-blocks", "256"])
     _check_common(d, 2, 1)
     cpu = d["cpu_baseline"]
     assert isinstance(cpu, dict)
@@ -60,8 +60,41 @@ def ro_rate(d):
 
 
 @pytest.mark.gpu
+def test_plain_run_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): the line carries the headline fields and the step's own kernels, no CPU
+    baseline and no side leg; --dump-outputs writes the last step's outputs as float32 .npy files, and they
+    are the right bytes: the repairs equal the CPU oracle's for the sampled blocks, every recovered row
+    equals the source it stands for."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    from oracle_py import Oracle, synth_bytes
+    nb, k, r, L = 2048, 16, 4, 1200
+    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--blocks", str(nb), "--dump-outputs", str(tmp_path)])
+    _check_common(d, 3, 1)
+    assert d["cpu_baseline"] is None
+    assert sorted(d["legs"]) == ["rlc_decode_k16_e4", "rlc_encode_k16_r4"]
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert sorted(got) == ["recovered_mask", "recovered_rows", "repairs", "sample_blocks", "status"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    idx = got["sample_blocks"].astype(np.int64)
+    n = len(idx)
+    assert n == min(nb, 1024) and np.all(np.diff(idx) > 0) and idx[-1] < nb
+    assert got["repairs"].shape == (n, r, L) and got["recovered_rows"].shape == (n, r, L)
+    assert got["status"].shape == (nb,) and got["recovered_mask"].shape == (n, 128)
+    src = synth_bytes(nb * k * L, 0x5EEDF3C0).reshape(nb, k, L)
+    assert np.array_equal(got["repairs"], Oracle().rlc_encode_batch(src, r, 0)[idx])
+    ok = got["status"][idx] == 0
+    assert ok.sum() >= 0.9 * n  # the rest: singular draws and the reference's own crash patterns
+    mask = got["recovered_mask"][ok]
+    assert np.all(mask.sum(1) == 4) and not mask[:, k:].any()
+    lost = np.nonzero(mask)[1].reshape(-1, 4)  # ascending per block: the packed rows' order
+    assert np.array_equal(got["recovered_rows"][ok], src[idx[ok, None], lost])
+
+
+@pytest.mark.gpu
 def test_bench_line_k32r8():
-    d = _run(["--config", "k32r8", "--steps", "1", "--warmup", "1", "--no-cpu"])
+    d = _run(["--full", "--config", "k32r8", "--steps", "1", "--warmup", "1", "--no-cpu"])
     _check_common(d, 1, 1, scaling="strong")
     assert d["cpu_baseline"] is None
     assert "k32" in d["roofline"]["kernel"] or "<8," in d["roofline"]["kernel"]

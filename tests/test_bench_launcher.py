@@ -34,7 +34,7 @@ def _line(out):
 @pytest.mark.skipif(not os.path.exists(ORACLE), reason="oracle not built (make -C oracle)")
 @pytest.mark.parametrize("config", ["k16", "k32r8"])
 def test_spawn_path_two_ranks(config):
-    p = _run(["--gpus", "2", "--config", config, "--dry-run", "--steps", "2", "--warmup", "1",
+    p = _run(["--gpus", "2", "--full", "--config", config, "--dry-run", "--steps", "2", "--warmup", "1",
               "--cpu-blocks", "64", "--cpu-seconds", "0.5"], {"PQUIC_BENCH_SHARE_GPU": "1"})
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
@@ -46,7 +46,7 @@ def test_spawn_path_two_ranks(config):
 @pytest.mark.skipif(not os.path.exists(ORACLE), reason="oracle not built (make -C oracle)")
 @pytest.mark.parametrize("config", ["k16", "k32r8"])
 def test_single_rank_carries_the_cpu_baseline(config):
-    p = _run(["--gpus", "1", "--config", config, "--dry-run", "--steps", "2", "--warmup", "1",
+    p = _run(["--gpus", "1", "--full", "--config", config, "--dry-run", "--steps", "2", "--warmup", "1",
               "--cpu-blocks", "64", "--cpu-seconds", "0.5"])
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
@@ -80,6 +80,15 @@ def test_single_gpu_dry_run_line():
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
     assert d["n_gpus"] == 1 and d["cpu_baseline"] is None
+
+
+def test_plain_run_measures_no_cpu_baseline():
+    """Without --full the benchmark does only what its headline figure needs: no CPU baseline, though
+    --no-cpu is not given."""
+    p = _run(["--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "1"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _line(p.stdout)
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["cpu_baseline"] is None
 
 
 def test_launcher_never_opens_the_gpu():

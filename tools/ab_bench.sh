@@ -7,7 +7,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for v in "$@"; do
   if [ "$v" = main ]; then lib=pquic_amd/lib/libpquic_fec.so; else lib=pquic_amd/lib/variants/$v/libpquic_fec.so; fi
-  PQUIC_AMD_LIB=$PWD/$lib timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu --no-pcie > $OUT/bench_$v.log 2>&1 || { tail $OUT/bench_$v.log; exit 1; }
+  PQUIC_AMD_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-cpu --no-pcie > $OUT/bench_$v.log 2>&1 || { tail $OUT/bench_$v.log; exit 1; }
   python - "$v" "$OUT/bench_$v.log" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

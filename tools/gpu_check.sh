@@ -12,7 +12,7 @@ tail -3 $OUT/pytest_gpu.log
 grep -q "pytest_rc=0" $OUT/pytest_gpu.log || exit 1
 timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 500 python bench.py "$@" > $OUT/bench.log 2>&1 || { tail $OUT/bench.log; exit 1; }
+timeout -k 10 500 python bench.py --full "$@" > $OUT/bench.log 2>&1 || { tail $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log
 # the headline workload again under rocprofv3 (kernel trace only, no side legs): its own bench line
 # (bench_prof.log) and the kernel statistics come from the same process and the same launches
