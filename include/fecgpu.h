@@ -49,6 +49,9 @@ extern "C" {
 #define FECGPU_BLOCK_REF_UB    2   /* erasure pattern on which the reference dereferences
                                       x[-1] (rlc_fec_scheme_gf256.c:74-77) or a NULL repair
                                       (xor_fec_scheme.c:50-51): no output, flagged          */
+#define FECGPU_BLOCK_SINGULAR  3   /* full-rank mode only (fecgpu_rlc_decode_full): the received
+                                      repairs have rank < the number of missing sources, so the
+                                      block is not determined: no output, recovered[] = 0     */
 
 #define FECGPU_MAX_K 128           /* presence masks are 2 x u64 per block               */
 #define FECGPU_MAX_R 128
@@ -172,6 +175,36 @@ int fecgpu_rlc_decode_seeded(void *src, const void *rep, uint64_t nblocks, uint3
                              const uint64_t *rep_present, uint8_t *status, uint64_t *recovered, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/* Full-rank RLC decode (opt-in; fecgpu_rlc_decode and its kin stay reference-faithful, bit for bit).
+ * The reference's elimination uses the first n = k - received sources repairs, sorts the rows once,
+ * never re-pivots and walks off its array on a zero pivot (FECGPU_BLOCK_REF_UB) -- on 1-5 % of random
+ * erasure patterns, almost all of which the received symbols determine.  Full mode recovers every block
+ * they determine.  Per block, with the masks clipped to k and r and m = received repairs:
+ *   FECGPU_BLOCK_NOTHING    the same preconditions as fecgpu_rlc_decode (r == 0, no source missing, or
+ *                           received sources + m < k);
+ *   FECGPU_BLOCK_RECOVERED  the m x n matrix of the received repairs' TinyMT32 rows, restricted to the
+ *                           missing columns, has rank n: every missing source is solved and written.  The
+ *                           solution is unique, so the bytes are the original sources (and
+ *                           fecgpu_rlc_decode's bytes wherever that recovers).  Exactly n received repairs
+ *                           are used, the lowest-index independent set; absent and unused repairs are
+ *                           never read.  recovered[] has the bit of every missing source whose bytes are
+ *                           not all zero; an all-zero one is written as zeros with its bit clear (as in
+ *                           reference mode), but it never hides another symbol;
+ *   FECGPU_BLOCK_SINGULAR   rank < n: nothing is written for the block, recovered[] is 0.
+ * FECGPU_BLOCK_REF_UB is never returned.  rep_seed selects the seeding: non-NULL, every equation is seeded
+ * by rep_seed[b * r + i] as in fecgpu_rlc_decode_seeded (fbn_base and fbn are ignored); NULL, by
+ * (fbn_b << 8) | i as in fecgpu_rlc_decode.  Workspace, masks, status and recovered as fecgpu_rlc_decode.
+ * fecgpu_rlc_decode_plan_full writes the same plan records as fecgpu_rlc_decode_plan (the reference plan,
+ * then a fix-up pass that re-plans the blocks it gave up on) and pairs with fecgpu_rlc_decode_apply,
+ * _apply_to and _apply_packed; fecgpu_rlc_decode_full is plan_full + apply, always as separate launches. */
+int fecgpu_rlc_decode_plan_full(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t fbn_base, const uint32_t *fbn,
+                                const uint32_t *rep_seed, const uint64_t *src_present, const uint64_t *rep_present,
+                                void *workspace, size_t workspace_bytes, void *stream);
+int fecgpu_rlc_decode_full(void *src, const void *rep, uint64_t nblocks, uint32_t k, uint32_t r,
+                           uint32_t symbol_size, uint32_t fbn_base, const uint32_t *fbn, const uint32_t *rep_seed,
+                           const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                           uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream);
+
 /* XOR decode (r == 1), same conventions. */
 int fecgpu_xor_decode(void *src, const void *rep, uint64_t nblocks, uint32_t k,
                       uint32_t symbol_size, const uint64_t *src_present,
@@ -209,6 +242,11 @@ int fecgpu_rlc_decode_host_seeded(fecgpu_host_ctx_t *ctx, void *src, const void 
                                   uint32_t k, uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
                                   const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
                                   uint64_t *recovered);
+/* host-resident fecgpu_rlc_decode_full: fbn / rep_seed are host arrays ([nblocks] / [nblocks][r]) */
+int fecgpu_rlc_decode_host_full(fecgpu_host_ctx_t *ctx, void *src, const void *rep, uint64_t nblocks,
+                                uint32_t k, uint32_t r, uint32_t symbol_size, uint32_t fbn_base,
+                                const uint32_t *fbn, const uint32_t *rep_seed, const uint64_t *src_present,
+                                const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
 /* fecgpu_rlc_encode_rows from the host: the row tables and fbn[] are host arrays (page-locked arrays
  * are read in place, others are copied), the rows themselves must be device-accessible. */
 int fecgpu_rlc_encode_rows_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint64_t *rep_rows,

@@ -195,7 +195,7 @@ struct WsLayout {
   uint32_t off_unk, off_sel, off_slot, off_nz, off_D, off_dep, stride;
 };
 
-__host__ __device__ static inline uint32_t pad16(uint32_t x) { return (x + 15u) & ~15u; }
+__host__ __device__ constexpr static inline uint32_t pad16(uint32_t x) { return (x + 15u) & ~15u; }
 
 __host__ __device__ static inline WsLayout ws_layout(uint32_t k, uint32_t r) {
   WsLayout w;
@@ -706,6 +706,215 @@ __global__ __launch_bounds__(64) void k_rlc_plan(uint64_t nblocks, int k, int r,
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   plan_load_tables(lds);
   for (uint64_t b = blockIdx.x; b < nblocks; b += gridDim.x) plan_wave_block(b, k, r, fbn_base, fbn, seeds, sp, rp, ws, lds);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Full-rank plan (fecgpu_rlc_decode_plan_full): the fix-up pass after a reference plan.  The
+// reference's elimination sorts rows once and never re-pivots, so it meets a zero pivot on systems
+// that are perfectly solvable (FECGPU_BLOCK_REF_UB), and it only ever looks at the first n received
+// repairs.  This pass re-plans those blocks from ALL m received repairs: one wave keeps the system
+// [A | V] of the repairs accepted so far in reduced row echelon form in LDS and offers it the
+// received repairs in ascending order; a repair whose row reduces to zero on the missing columns is
+// dependent on the accepted ones and is skipped, so the n accepted repairs are the lowest-index
+// independent set.  With n accepted rows A is the identity and row t of V is the solution row of
+// unknown pc[t].  Fewer than n: FECGPU_BLOCK_SINGULAR, nothing recovered.
+// A lane owns columns lane + 64 q (q < 4; n + k <= 256) of the candidate row in registers and of
+// every basis row in LDS.  Because the basis is fully reduced (a basis row is zero in every other
+// pivot column), the factors of a candidate against all basis rows are its own entries at the pivot
+// columns: one pass over the basis per candidate, no dependent chain across basis rows.
+// LDS: log/exp | R[r][kpad] TinyMT32 rows of the received repairs | B[em][wpad] basis rows
+//      (wpad = pad16(em + k): A columns 0..n-1, then V) | unk, cand, sel, pc, rowof int[128] | fac[128].
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ constexpr static inline size_t plan_full_lds_bytes(uint32_t k, uint32_t r) {
+  const uint32_t em = k < r ? k : r;
+  return 768 + (size_t)r * pad16(k) + (size_t)em * pad16(em + k) + 4 * (128 * 5) + 128 + 16;
+}
+
+// One block's full-rank plan by one wave of a one-wave workgroup.  `lds` holds the log/exp tables at
+// 0 and room for plan_full_lds_bytes(k, r).  Every lane must call it; control flow is wave-uniform.
+__device__ void plan_full_wave_block(uint64_t b, int k, int r, uint32_t fbn_base, const uint32_t *fbn,
+                                     const uint32_t *seeds, const uint64_t *sp, const uint64_t *rp, uint8_t *ws,
+                                     uint8_t *lds) {
+  const WsLayout L = ws_layout((uint32_t)k, (uint32_t)r);
+  const int lane = threadIdx.x;
+  const int em = (int)L.em;
+  const int kpad = (int)pad16((uint32_t)k);
+  const int wpad = (int)pad16((uint32_t)(em + k));
+  uint8_t *EXP = lds, *LOG = lds + 512;
+  uint8_t *R = lds + 768;
+  uint8_t *B = R + (size_t)r * kpad;
+  int *unk = reinterpret_cast<int *>(B + (size_t)em * wpad);
+  int *cand = unk + 128, *sel = unk + 256, *pc = unk + 384, *rowof = unk + 512;
+  uint8_t *fac = reinterpret_cast<uint8_t *>(unk + 640);
+  uint8_t *h = ws + b * (uint64_t)L.stride;
+
+  uint64_t s0 = sp[2 * b], s1 = sp[2 * b + 1], q0 = rp[2 * b], q1 = rp[2 * b + 1];
+  clip128(s0, s1, k);
+  clip128(q0, q1, r);
+  const int cur_ss = __popcll(s0) + __popcll(s1);
+  const int m = __popcll(q0) + __popcll(q1);
+  __syncthreads();  // the previous block's LDS reads are done
+  if (r == 0 || cur_ss == k || cur_ss + m < k) {
+    if (lane == 0) { h[0] = FECGPU_BLOCK_NOTHING; h[1] = 0; }
+    return;
+  }
+  const int n = k - cur_ss;  // unknowns; n <= m, n <= em
+  uint64_t m0 = ~s0, m1 = ~s1;
+  clip128(m0, m1, k);
+  for (int j = lane; j < k; j += 64)
+    if (bit128(m0, m1, j)) unk[rank128(m0, m1, j)] = j;
+  for (int i = lane; i < r; i += 64)
+    if (bit128(q0, q1, i)) cand[rank128(q0, q1, i)] = i;
+  __syncthreads();
+  const uint32_t f = block_fbn(b, fbn_base, fbn);
+  for (int e = lane; e < m; e += 64) {  // TinyMT32 row of every received repair
+    Tmt t;
+    tmt_init(t, repair_seed(seeds, b, r, f, (uint32_t)cand[e]));
+    for (int j = 0; j < k; j++) R[e * kpad + j] = tmt_coef(t);
+  }
+  __syncthreads();
+  const int w = n + k;
+  const int nq = (w + 63) >> 6;  // column registers in use
+  int cnt = 0;
+  for (int e = 0; e < m && cnt < n; e++) {
+    if (m - e < n - cnt) break;  // too few repairs left to reach rank n
+    const uint8_t *row = R + e * kpad;
+    // the candidate's factor against basis row t is its entry at pivot column pc[t] (log, 255 = zero)
+    for (int t = lane; t < cnt; t += 64) {
+      const uint32_t a = row[unk[pc[t]]];
+      fac[t] = a ? LOG[a] : (uint8_t)255;
+    }
+    __syncthreads();
+    // candidate row as it would stand at position cnt: A[u] = row[unk[u]]; V[j] = row[j] for a present
+    // source, and 1 at its own slot unk[cnt] (the repair itself is the input there), minus the basis
+    // (loads unconditional, products selected afterwards: the basis rows' lookups are independent and
+    // overlap, where a branch per row would leave one chain of four dependent LDS reads after the other)
+    uint32_t wv[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      if (q >= nq) continue;  // wave-uniform
+      const int c = lane + 64 * q;
+      const int cc = c < w ? c : w - 1;
+      uint32_t v;
+      if (cc < n) v = row[unk[cc]];
+      else {
+        const int j = cc - n;
+        v = bit128(m0, m1, j) ? (uint32_t)(unk[cnt] == j) : (uint32_t)row[j];
+      }
+#pragma unroll 4
+      for (int t = 0; t < cnt; t++) {
+        const uint32_t ft = fac[t];
+        const uint32_t bv = B[t * wpad + cc];
+        const uint32_t pr = EXP[ft + LOG[bv]];
+        v ^= (bv != 0 && ft != 255u) ? pr : 0u;
+      }
+      wv[q] = c < w ? v : 0u;
+    }
+    // pivot: the first missing column where the reduced candidate is non-zero (A columns: c < n <= 128)
+    const uint64_t z0 = __ballot(lane < n && wv[0] != 0);
+    const uint64_t z1 = __ballot(lane + 64 < n && wv[1] != 0);
+    __syncthreads();  // fac[] has been read by every lane
+    if ((z0 | z1) == 0) continue;  // dependent on the accepted repairs: never read by the data pass
+    const int p = z0 ? __ffsll((unsigned long long)z0) - 1 : 64 + __ffsll((unsigned long long)z1) - 1;
+    const uint32_t pv = p < 64 ? (uint32_t)__shfl((int)wv[0], p, 64) : (uint32_t)__shfl((int)wv[1], p - 64, 64);
+    const uint32_t li = 255u - LOG[pv];  // log of 1 / pivot
+#pragma unroll
+    for (int q = 0; q < 4; q++) {  // normalised row into the basis
+      const int c = lane + 64 * q;
+      wv[q] = wv[q] ? (uint32_t)EXP[LOG[wv[q]] + li] : 0u;
+      if (c < w) B[cnt * wpad + c] = (uint8_t)wv[q];
+    }
+    if (lane == 0) { pc[cnt] = p; sel[cnt] = cand[e]; }
+    for (int t = lane; t < cnt; t += 64) {  // clear column p of the earlier basis rows
+      const uint32_t a = B[t * wpad + p];
+      fac[t] = a ? LOG[a] : (uint8_t)255;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      if (q >= nq) continue;  // wave-uniform
+      const int c = lane + 64 * q;
+      const int cc = c < w ? c : w - 1;
+      const bool live = c < w && wv[q] != 0;
+      const uint32_t lw = LOG[wv[q]];
+      int t = 0;
+      for (; t + 4 <= cnt; t += 4) {  // four rows' loads before their stores, so the lookups overlap
+        uint32_t ft[4], old[4], pr[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) { ft[u] = fac[t + u]; old[u] = B[(t + u) * wpad + cc]; }
+#pragma unroll
+        for (int u = 0; u < 4; u++) pr[u] = EXP[ft[u] + lw];
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+          if (live && ft[u] != 255u) B[(t + u) * wpad + cc] = (uint8_t)(old[u] ^ pr[u]);
+      }
+      for (; t < cnt; t++) {
+        const uint32_t ft = fac[t];
+        if (live && ft != 255u) B[t * wpad + cc] ^= EXP[ft + lw];
+      }
+    }
+    cnt++;
+    __syncthreads();
+  }
+  if (cnt < n) {  // the received repairs do not determine the block
+    if (lane == 0) { h[0] = FECGPU_BLOCK_SINGULAR; h[1] = 0; }
+    return;
+  }
+  for (int t = lane; t < n; t += 64) rowof[pc[t]] = t;
+  __syncthreads();
+  for (int x = lane; x < n * n; x += 64) {  // a full-rank solution has no undetermined unknowns
+    const int i = x / n, u = x - i * n;
+    h[L.off_dep + i * em + u] = 0;
+  }
+  for (int x = lane; x < n * k; x += 64) {
+    const int i = x / k, j = x - i * k;
+    h[L.off_D + i * k + j] = B[rowof[i] * wpad + n + j];
+  }
+  PlanLds P{};
+  P.unk = unk;
+  P.sel = sel;
+  plan_wave_finish(h, L, P, k, n, m0, m1);
+}
+
+// Fix-up pass over the records of a reference plan: strips of 64 records per wave, lane l reading
+// the header of block base + l.  Recovered records are already the unique solution (non-zero pivots
+// mean the system is invertible); only their dependency flags are cleared, so that a zero symbol
+// hides no other.  Records the reference elimination gave up on are planned again from every
+// received repair, one after the other by the whole wave.  A re-plan is one wave's dependent chain
+// (tens of microseconds), so a strip is shared by `parts` waves -- each reads the 64 headers and takes
+// the flagged records g with g % parts == its number, and its slice of the clearing -- and the host picks `parts` so that a
+// batch of few strips still spreads its flagged blocks over the device.
+__global__ __launch_bounds__(64) void k_rlc_plan_full(uint64_t nblocks, int k, int r, uint32_t fbn_base,
+                                                      const uint32_t *fbn, const uint32_t *seeds, const uint64_t *sp,
+                                                      const uint64_t *rp, uint8_t *ws, uint32_t parts) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  plan_load_tables(lds);
+  __syncthreads();
+  const WsLayout L = ws_layout((uint32_t)k, (uint32_t)r);
+  const int lane = threadIdx.x;
+  const uint32_t depw = pad16(L.em * L.em) >> 2;  // dependency region in 32-bit words
+  const uint64_t nitems = ((nblocks + 63) / 64) * parts;
+  for (uint64_t it = blockIdx.x; it < nitems; it += gridDim.x) {
+    const uint64_t base = (it / parts) * 64;
+    const uint32_t part = (uint32_t)(it % parts);
+    int st = FECGPU_BLOCK_NOTHING;
+    if (base + lane < nblocks) st = ws[(base + lane) * (uint64_t)L.stride];
+    const uint64_t rec = __ballot(st == FECGPU_BLOCK_RECOVERED);
+    uint64_t todo = __ballot(st == FECGPU_BLOCK_REF_UB);
+    for (uint32_t x = part * 64 + lane; x < 64 * depw; x += 64 * parts) {
+      const uint32_t g = x / depw, o = x - g * depw;
+      if ((rec >> g) & 1)
+        reinterpret_cast<uint32_t *>(ws + (base + g) * (uint64_t)L.stride + L.off_dep)[o] = 0u;
+    }
+    // record g belongs to wave g % parts whatever the others see: a wave that reads the headers late
+    // finds some of them already re-planned by its neighbours, so a count of the flagged records would differ
+    // from wave to wave; only the owner ever rewrites a flagged header, so the owner always sees it flagged
+    while (todo) {
+      const int g = __ffsll((unsigned long long)todo) - 1;
+      todo &= todo - 1;
+      if ((uint32_t)g % parts == part) plan_full_wave_block(base + g, k, r, fbn_base, fbn, seeds, sp, rp, ws, lds);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3445,6 +3654,34 @@ int fecgpu_rlc_decode_plan_seeded(uint64_t nblocks, uint32_t k, uint32_t r, cons
                           workspace_bytes, stream);
 }
 
+// Full mode's plan: the reference plan (whatever kernel the "plan" knob picks), then the fix-up pass
+// over its records.  seeds == nullptr: (fbn << 8) | i.
+static int decode_plan_full_impl(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t fbn_base, const uint32_t *fbn,
+                                 const uint32_t *seeds, const uint64_t *src_present, const uint64_t *rep_present,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+  int rc = decode_plan_impl(nblocks, k, r, fbn_base, fbn, seeds, src_present, rep_present, workspace,
+                            workspace_bytes, stream);
+  if (rc || nblocks == 0 || r == 0) return rc;  // r == 0: every record says "nothing to recover"
+  // 52 KiB at k = r = 128, the largest shape: the default dynamic-LDS limit holds for every shape
+  const size_t lds = plan_full_lds_bytes(k, r);
+  static_assert(plan_full_lds_bytes(FECGPU_MAX_K, FECGPU_MAX_R) <= 65536, "full plan LDS within the default limit");
+  // waves per strip of 64 records: enough of them that a batch of few strips still puts its flagged blocks
+  // (a few per strip) on different waves; one per strip once the strips alone fill the device
+  const uint64_t strips = (nblocks + 63) / 64;
+  const uint32_t parts = (uint32_t)(strips >= 8192 ? 1 : (8192 + strips - 1) / strips > 16 ? 16 : (8192 + strips - 1) / strips);
+  hipLaunchKernelGGL(k_rlc_plan_full, dim3(grid_for(strips * parts)), dim3(64), lds, (hipStream_t)stream, nblocks,
+                     (int)k, (int)r, fbn_base, fbn, seeds, src_present, rep_present, (uint8_t *)workspace, parts);
+  HIPCHK(hipGetLastError());
+  return FECGPU_OK;
+}
+
+int fecgpu_rlc_decode_plan_full(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t fbn_base, const uint32_t *fbn,
+                                const uint32_t *rep_seed, const uint64_t *src_present, const uint64_t *rep_present,
+                                void *workspace, size_t workspace_bytes, void *stream) {
+  return decode_plan_full_impl(nblocks, k, r, rep_seed ? 0 : fbn_base, rep_seed ? nullptr : fbn, rep_seed,
+                               src_present, rep_present, workspace, workspace_bytes, stream);
+}
+
 static int launch_finalize(uint64_t nblocks, uint32_t k, uint32_t r, uint8_t *status, uint64_t *recovered,
                            const uint8_t *ws, hipStream_t s) {
   const uint32_t fgrid = (uint32_t)((nblocks + 255) / 256 < 65536 ? (nblocks + 255) / 256 : 65536);
@@ -3570,11 +3807,16 @@ constexpr uint64_t kDecodeSmallMaxBlocks = 64;
 static int decode_impl(const void *src, const void *rep, void *dst, uint64_t nblocks, uint32_t k, uint32_t r,
                        uint32_t L, uint32_t fbn_base, const uint32_t *fbn, const uint32_t *seeds,
                        const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered, void *ws,
-                       size_t wsb, hipStream_t s) {
+                       size_t wsb, hipStream_t s, int full = 0) {
   int rc = decode_args(src, rep, nblocks, k, r, L, sp, rp, status, recovered, ws, wsb);
   if (rc || nblocks == 0) return rc;
   if (!dst) return set_err(FECGPU_ERR_INVALID, "%s", "NULL output buffer");
   if ((uintptr_t)dst % 4) return set_err(FECGPU_ERR_INVALID, "%s", "output buffer must be 4-byte aligned");
+  if (full) {  // full-rank mode: the one-launch paths below plan in reference mode inside the kernel
+    rc = decode_plan_full_impl(nblocks, k, r, fbn_base, fbn, seeds, sp, rp, ws, wsb, s);
+    if (rc) return rc;
+    return decode_apply_impl(src, rep, dst, nblocks, k, r, L, status, recovered, ws, wsb, s);
+  }
   const WsLayout WL = ws_layout(k, r);
   // a few blocks with their rows in LDS: one launch, the plan beside the row fetch
   if (nblocks <= kSmallLdsMaxBlocks && r > 0 && WL.em <= 16 && knob(K_PLAN) == 0 && knob(K_SMALL_LDS)) {
@@ -3633,13 +3875,22 @@ int fecgpu_rlc_decode_seeded(void *src, const void *rep, uint64_t nblocks, uint3
                      status, recovered, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-// host_path.hip: decode with the recovered rows to dst (library-internal)
+int fecgpu_rlc_decode_full(void *src, const void *rep, uint64_t nblocks, uint32_t k, uint32_t r,
+                           uint32_t symbol_size, uint32_t fbn_base, const uint32_t *fbn, const uint32_t *rep_seed,
+                           const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                           uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream) {
+  return decode_impl(src, rep, src, nblocks, k, r, symbol_size, rep_seed ? 0 : fbn_base, rep_seed ? nullptr : fbn,
+                     rep_seed, src_present, rep_present, status, recovered, workspace, workspace_bytes,
+                     (hipStream_t)stream, 1);
+}
+
+// host_path.hip: decode with the recovered rows to dst (library-internal); full != 0: full-rank mode
 extern "C" __attribute__((visibility("hidden"))) int fecgpu_rlc_decode_to_internal(
     const void *src, const void *rep, void *dst, uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L,
     uint32_t fbn_base, const uint32_t *fbn, const uint32_t *seeds, const uint64_t *sp, const uint64_t *rp,
-    uint8_t *status, uint64_t *recovered, void *ws, size_t wsb, void *stream) {
+    uint8_t *status, uint64_t *recovered, void *ws, size_t wsb, void *stream, int full) {
   return decode_impl(src, rep, dst, nblocks, k, r, L, fbn_base, fbn, seeds, sp, rp, status, recovered, ws, wsb,
-                     (hipStream_t)stream);
+                     (hipStream_t)stream, full);
 }
 
 static int xor_decode_impl(void *src, const void *rep, void *dst, uint64_t nblocks, uint32_t k, uint32_t symbol_size,

@@ -172,7 +172,7 @@ int fecgpu_knob_zc_read(void);  // fec_engine.hip (library-internal, C linkage)
 int fecgpu_rlc_decode_to_internal(const void *src, const void *rep, void *dst, uint64_t nblocks, uint32_t k,
                                   uint32_t r, uint32_t L, uint32_t fbn_base, const uint32_t *fbn,
                                   const uint32_t *seeds, const uint64_t *sp, const uint64_t *rp, uint8_t *status,
-                                  uint64_t *recovered, void *ws, size_t wsb, void *stream);  // fec_engine.hip
+                                  uint64_t *recovered, void *ws, size_t wsb, void *stream, int full);  // fec_engine.hip
 int fecgpu_knob_window_sc(void);  // fec_engine.hip (library-internal)
 static bool zc_read() { return fecgpu_knob_zc_read() != 0; }
 
@@ -441,10 +441,12 @@ int fecgpu_xor_encode_host(fecgpu_host_ctx_t *c, const void *src, void *rep, uin
 // rep_present[n][2], recovered[n][2] (u64), status[n] (u8)
 static size_t aux_bytes(uint64_t n, uint32_t nseed) { return ((n * 4 * nseed + 15) & ~(size_t)15) + n * 16 * 3 + n; }
 
-// seeds: rep_seed[nblocks][r] (per-repair FPID seeds) or nullptr (block numbers from fbn / fbn_base)
+// seeds: rep_seed[nblocks][r] (per-repair FPID seeds) or nullptr (block numbers from fbn / fbn_base);
+// full != 0: full-rank mode (fecgpu_rlc_decode_full) instead of the reference's elimination
 static int decode_host(fecgpu_host_ctx_t *c, bool xr, void *src, const void *rep, uint64_t nblocks, uint32_t k,
                        uint32_t r, uint32_t L, uint32_t fbn_base, const uint32_t *fbn, const uint32_t *seeds,
-                       const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+                       const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered,
+                       int full = 0) {
   if (!c || !src || !rep || !sp || !rp || !status || !recovered) return FECGPU_ERR_INVALID;
   if (!nblocks) return FECGPU_OK;
   std::lock_guard<std::mutex> g(c->mu);
@@ -518,7 +520,7 @@ static int decode_host(fecgpu_host_ctx_t *c, bool xr, void *src, const void *rep
       rc = fecgpu_rlc_decode_to_internal(in_src, in_rep, zdst ? zdst + b0 * sb : s.d_src, m, k, r, L,
                                          seeds ? 0u : (uint32_t)((fbn_base + b0) & 0xffffffu),
                                          (!seeds && fbn) ? d_fbn : nullptr, seeds ? d_fbn : nullptr, d_sp, d_rp,
-                                         d_st, d_rec, s.d_ws, s.cap_ws, s.st);
+                                         d_st, d_rec, s.d_ws, s.cap_ws, s.st, full);
     }
     if (rc) break;
     if (!zdst) LCHK(hipMemcpyAsync((uint8_t *)src + b0 * sb, s.d_src, m * sb, hipMemcpyDeviceToHost, s.st));
@@ -541,6 +543,14 @@ int fecgpu_rlc_decode_host_seeded(fecgpu_host_ctx_t *c, void *src, const void *r
                                   const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
   if (nblocks && r && !rep_seed) return FECGPU_ERR_INVALID;
   return decode_host(c, false, src, rep, nblocks, k, r, L, 0, nullptr, rep_seed, sp, rp, status, recovered);
+}
+
+int fecgpu_rlc_decode_host_full(fecgpu_host_ctx_t *c, void *src, const void *rep, uint64_t nblocks, uint32_t k,
+                                uint32_t r, uint32_t L, uint32_t fbn_base, const uint32_t *fbn,
+                                const uint32_t *rep_seed, const uint64_t *sp, const uint64_t *rp, uint8_t *status,
+                                uint64_t *recovered) {
+  return decode_host(c, false, src, rep, nblocks, k, r, L, rep_seed ? 0 : fbn_base, rep_seed ? nullptr : fbn,
+                     rep_seed, sp, rp, status, recovered, 1);
 }
 
 int fecgpu_rlc_decode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint64_t *rep_rows,

@@ -14,7 +14,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PQUIC_AMD_LIB") or os.path.join(PKG, "lib", "libpquic_fec.so")
 
 OK, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM = 0, -1, -2, -3, -4
-BLOCK_RECOVERED, BLOCK_NOTHING, BLOCK_REF_UB = 0, 1, 2
+BLOCK_RECOVERED, BLOCK_NOTHING, BLOCK_REF_UB, BLOCK_SINGULAR = 0, 1, 2, 3
 
 _lib = None
 
@@ -95,6 +95,10 @@ def load_library(path: str = LIB_PATH, private: bool = False):
     if hasattr(L, "fecgpu_rlc_decode_rows"):
         L.fecgpu_rlc_decode_rows.argtypes = [v, v, u64, u32, u32, u32, v, v, v, v, v, v, sz, v]
         L.fecgpu_rlc_decode_rows_host.argtypes = [v, v, v, u64, u32, u32, u32, v, v, v, v, v]
+    if hasattr(L, "fecgpu_rlc_decode_full") or not private:  # a private (A/B) load may be an older build
+        L.fecgpu_rlc_decode_plan_full.argtypes = [u64, u32, u32, u32, v, v, v, v, v, sz, v]
+        L.fecgpu_rlc_decode_full.argtypes = [v, v, u64, u32, u32, u32, u32, v, v, v, v, v, v, v, sz, v]
+        L.fecgpu_rlc_decode_host_full.argtypes = [v, v, v, u64, u32, u32, u32, u32, v, v, v, v, v, v]
     if not private:
         _lib = L
     return L
@@ -226,6 +230,30 @@ class Engine:
             "fecgpu_rlc_decode_seeded")
         return status, recovered
 
+    def rlc_decode_full(self, src, rep, src_present, rep_present, status, recovered, k: int, r: int,
+                        L: int, nblocks: int | None = None, fbn_base: int = 0, fbn=None, rep_seed=None,
+                        workspace=None, stream=None):
+        """fecgpu_rlc_decode_full: full-rank mode -- every block the received symbols determine is
+        recovered (BLOCK_RECOVERED), the others are BLOCK_SINGULAR; never BLOCK_REF_UB.  rep_seed (u32
+        device array [nblocks][r]) selects the seeded form, else (fbn << 8) | i from fbn / fbn_base."""
+        nb = nblocks if nblocks is not None else src.numel() // (k * L)
+        if workspace is None:
+            workspace = self.alloc_workspace(nb, k, r)
+        self._check(self.lib.fecgpu_rlc_decode_full(
+            _addr(src), _addr(rep), nb, k, r, L, fbn_base, _addr(fbn), _addr(rep_seed), _addr(src_present),
+            _addr(rep_present), _addr(status), _addr(recovered), _addr(workspace), workspace.numel(),
+            self._stream(stream)), "fecgpu_rlc_decode_full")
+        return status, recovered
+
+    def rlc_decode_plan_full(self, src_present, rep_present, k, r, nblocks, workspace, fbn_base=0, fbn=None,
+                             rep_seed=None, stream=None):
+        """fecgpu_rlc_decode_plan_full: full-rank mode's plan; pairs with rlc_decode_apply, _apply_to and
+        _apply_packed."""
+        self._check(self.lib.fecgpu_rlc_decode_plan_full(nblocks, k, r, fbn_base, _addr(fbn), _addr(rep_seed),
+                                                         _addr(src_present), _addr(rep_present), _addr(workspace),
+                                                         workspace.numel(), self._stream(stream)),
+                    "fecgpu_rlc_decode_plan_full")
+
     def rlc_decode_stages(self, src, rep, src_present, rep_present, status, recovered, k, r, L, nblocks,
                           workspace, fbn_base=0, stream=None, events=None, dst=None, packed=False):
         """fecgpu_rlc_decode as its two stages (plan, apply); events[i] (if given) recorded before
@@ -348,3 +376,9 @@ class HostPath:
         self._chk(self.lib.fecgpu_rlc_decode_host_seeded(self.ctx, _addr(src), _addr(rep), nblocks, k, r, L,
                                                          _addr(seeds), _addr(sp), _addr(rp), _addr(status),
                                                          _addr(rec)), "fecgpu_rlc_decode_host_seeded")
+
+    def rlc_decode_full(self, src, rep, sp, rp, status, rec, nblocks, k, r, L, fbn_base=0, fbn=None, seeds=None):
+        """fecgpu_rlc_decode_host_full: full-rank mode on host buffers (fbn / seeds: host arrays)."""
+        self._chk(self.lib.fecgpu_rlc_decode_host_full(self.ctx, _addr(src), _addr(rep), nblocks, k, r, L, fbn_base,
+                                                       _addr(fbn), _addr(seeds), _addr(sp), _addr(rp),
+                                                       _addr(status), _addr(rec)), "fecgpu_rlc_decode_host_full")
