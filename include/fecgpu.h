@@ -347,22 +347,41 @@ int fecgpu_host_device_address(const void *p, size_t bytes, uint64_t *dev);
 int fecgpu_synth_fill(void *dst, uint64_t nbytes, uint64_t seed, uint64_t offset, void *stream);
 
 /* Experiment knobs (A/B runs, cross-checks of alternative kernels in the tests).  Every knob has
- * a measured default and only these calls change it (the library reads no environment variables;
- * tools/ab_inproc.py maps the FECGPU_* names of earlier rounds onto them).  Names and accepted values:
- * "plan" (0 auto, 1 wave in LDS, 2 lane, 3 reg, 4 tile, 5 wave in registers where it fits),
- * "interleave" (0/1), "group" (0 = defaults, else a cap on blocks per group), "enc_tile_rt" (0 =
- * default tiling, else 1/2/4/8/16) / "enc_tile_waves" (0..4), "zc_read" (0/1), "ring" (the LDS-ring
- * data path of 16-repair / 16-unknown tiles: 2 = default, 0 off), "window_sc" (window encode on the
- * shared-coefficient kernel: 0 never, 1 = default for overlapping windows, 2 wherever it applies),
- * "min_groups" (batches with fewer block groups than this stream fewer blocks per wave; default
- * 1024, 0 = the per-shape group sizes at any batch size), "chunk_waves" (symbols wider than one column
- * chunk coded by 4-wave workgroups over (block, chunk) items: 1 = default, 0 one wave per group),
- * "small_lds" (batches of <= 64 blocks with their rows staged in LDS: 1 = default, 0 the bitsliced
- * kernels), "block_svc" (the resident single-block service: 1 = default, 0 refused), "ws_lds" (the
- * recover data pass copies a group's plan records into LDS in one round trip: 1 = default, 0 reads
- * them in place), "dec_waves" (0 = default, n = at most n waves per SIMD for the register-prefetch
- * recover tiles).  Returns FECGPU_OK, or FECGPU_ERR_INVALID
- * for an unknown name or a value outside its range. */
+ * a measured default and only these calls change it.  The engine reads no environment variable; the
+ * batching adapter (pquic_fec_batch.h) reads three, once per batcher.  tools/ab_inproc.py maps the
+ * FECGPU_* names of earlier rounds onto the knobs.  Names, accepted values and defaults (the engine's
+ * table, FEC_KNOBS in fec_engine.hip):
+ *   "plan"             0..5: 0 auto (default), 1 wave in LDS, 2 lane, 3 reg, 4 tile, 5 wave in registers
+ *                      where it fits
+ *   "interleave"       0..3, default 1: bit 0 interleaved block groups, bit 1 XCD-aware group order
+ *   "group"            >= 0: 0 the per-shape group sizes (default), else a cap on blocks per group
+ *   "enc_tile_rt"      0 the default tiling by r (default), else 1, 2, 4, 8 or 16 repairs per tile
+ *   "enc_tile_waves"   0..4, default 0: waves per workgroup splitting a group's repairs (with enc_tile_rt)
+ *   "enc_block_waves"  1 (default), 2 or 4: waves per workgroup of the register-prefetch encode, each
+ *                      on its own block group
+ *   "zc_read"          0/1, default 1: page-locked host buffers read in place; 0 staged by copies
+ *   "ring"             2 (default) or 0: the LDS-ring data path of 16-repair / 16-unknown tiles on / off
+ *   "window_sc"        0..2: window encode on the shared-coefficient kernel never (0), for overlapping
+ *                      windows (1, default), wherever it applies (2)
+ *   "min_groups"       >= 0, default 1024: batches with fewer block groups than this stream fewer blocks
+ *                      per wave; 0 the per-shape group sizes at any batch size
+ *   "chunk_waves"      0/1, default 1: symbols wider than one column chunk coded by 4-wave workgroups
+ *                      over (block, chunk) items; 0 one wave per group
+ *   "small_lds"        0/1, default 1: batches of <= 64 blocks with their rows staged in LDS; 0 the
+ *                      bitsliced kernels
+ *   "block_svc"        0/1, default 1: the resident single-block service; 0 refuses every request
+ *   "ws_lds"           0/1, default 1: the recover data pass copies a group's plan records into LDS in
+ *                      one round trip; 0 reads them in place
+ *   "dec_waves"        0..8, default 0: at most n waves per SIMD for the register-prefetch recover tiles
+ *   "yield_slice_kb"   0..1048576, default 2304: zero-copy bulk calls run in slices of this many KiB of
+ *                      payload while the synchronous hooks are in use; 0 never slices
+ *   "yield_depth"      1..16, default 16: slices in flight at most
+ *   "yield_gate_us"    0..10000, default 0: a slice is held back at most this long while a hook request
+ *                      is pending
+ *   "yield_streams"    1..4, default 2: streams of the context the slices alternate over
+ *   "yield_always"     0/1, default 0: slice even when no hook has run lately
+ *   "yield_window_ms"  0..600000, default 100: the hooks count as in use for this long after a request
+ * Returns FECGPU_OK, or FECGPU_ERR_INVALID for an unknown name or a value its knob does not accept. */
 int fecgpu_set_knob(const char *name, int value);
 int fecgpu_get_knob(const char *name, int *value);
 

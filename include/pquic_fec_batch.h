@@ -66,7 +66,13 @@ typedef struct {
                                      * two or more were in flight (flushed at the first poll with one back) */
 } pquic_fec_batch_stats_t;
 
-/* NULL on failure (bad configuration, no device, out of pinned memory). */
+/* NULL on failure (bad configuration, no device, out of pinned memory).
+ * The adapter reads three environment variables, once per batcher, here (a value below the minimum
+ * counts as unset, one above the maximum as the maximum):
+ *   PQUIC_FEC_BATCH_STAGERS   copy threads, 1..16; default half the CPUs of the process's share, at least 2
+ *   PQUIC_FEC_BATCH_ENGINES   engine threads, each with its own host context and streams, 1..4; default 2
+ *   PQUIC_FEC_BATCH_PREFETCH  blocks ahead a completion prefetches the symbols it hands over, 0..64
+ *                             (0: off); default 8 */
 pquic_fec_batcher_t *pquic_fec_batcher_create(const pquic_fec_batch_cfg_t *cfg);
 /* Drains (completing every queued block) and frees. */
 void pquic_fec_batcher_destroy(pquic_fec_batcher_t *b);

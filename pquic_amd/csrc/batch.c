@@ -131,9 +131,7 @@ struct pquic_fec_batcher {
     pthread_cond_t cv_prov;
     job_t *spares;
     uint64_t stats_spares;         /* spares made (under mu) */
-    int reserve;                   /* idle jobs of a shape to keep, free + spare (PQUIC_FEC_BATCH_RESERVE, default 1) */
     uint32_t small_cap;            /* blocks of a job the caller allocates itself (0: full size; job_get) */
-    int hold;                      /* deadline_hold on (PQUIC_FEC_BATCH_HOLD=0 turns it off, A/B) */
     uint64_t next_seq;             /* caller thread: sequence number of the next flushed job */
     uint64_t collect_seq;          /* caller thread: the job whose completions come next */
     uint64_t jobs_back;            /* caller thread: flushed jobs completed and back in free_jobs */
@@ -378,8 +376,7 @@ static int count_fit(const job_t *j, size_t sb, size_t rb) {
  * (same shape, prepared for the same use) and leaves it in b->spares, where job_get finds it.  One spare
  * covers one job more in flight per allocation time (about 20 ms for a 4096-block k16 r4 job); a stall that
  * deepens the pipeline faster (the paced leg under a kernel trace: 1-2 caller allocations of 20-45 ms in 3 of
- * 12 runs, profiles/r06_paced_probe.log) makes the caller allocate.  That allocation is a small job (job_get);
- * PQUIC_FEC_BATCH_RESERVE > 1 has the provisioner keep more idle full-size jobs of the shape (free or spare). */
+ * 12 runs, profiles/r06_paced_probe.log) makes the caller allocate.  That allocation is a small job (job_get). */
 static void *prov_main(void *arg) {
     pquic_fec_batcher_t *b = arg;
     pthread_mutex_lock(&b->mu);
@@ -435,11 +432,10 @@ static job_t *job_get(pquic_fec_batcher_t *b, int op, int xor_scheme, uint32_t k
         b->free_jobs = j;
         return NULL;
     }
-    /* fewer idle jobs of this shape than the reserve: have the next one made off this thread */
-    const int idle = count_fit(b->free_jobs, sb, rb);
-    if (b->prov_started && idle < b->reserve) {
+    /* no idle job of this shape left, free or spare: have the next one made off this thread */
+    if (b->prov_started && !count_fit(b->free_jobs, sb, rb)) {
         pthread_mutex_lock(&b->mu);
-        if (!b->prov_want && idle + count_fit(b->spares, sb, rb) < b->reserve) {
+        if (!b->prov_want && !count_fit(b->spares, sb, rb)) {
             b->prov_want = 1;
             b->prov_op = op;
             b->prov_xor = xor_scheme;
@@ -819,6 +815,14 @@ static void *worker_main(void *arg) {
     return NULL;
 }
 
+/* The adapter's three environment settings (pquic_fec_batch.h), read once per batcher: the variable's
+ * value, at most `max`; `def` when it is unset or below `min`. */
+static int env_int(const char *name, int def, int min, int max) {
+    const char *s = getenv(name);
+    const int v = s ? atoi(s) : min - 1;
+    return v < min ? def : v > max ? max : v;
+}
+
 pquic_fec_batcher_t *pquic_fec_batcher_create(const pquic_fec_batch_cfg_t *cfg) {
     if (!cfg || cfg->batch_blocks < 1 || cfg->max_symbol < 1 || cfg->max_symbol > 32767 || cfg->nstreams < 1)
         return NULL;
@@ -827,13 +831,9 @@ pquic_fec_batcher_t *pquic_fec_batcher_create(const pquic_fec_batch_cfg_t *cfg) 
     b->cfg = *cfg;
     b->stride = fec_pad4(cfg->max_symbol);
     b->next_due = UINT64_MAX;
-    const char *pfs = getenv("PQUIC_FEC_BATCH_PREFETCH");  /* read once per batcher, like the thread counts */
-    b->pf = pfs && atoi(pfs) >= 0 ? (uint32_t)atoi(pfs) : 8;
-    if (b->pf > 64) b->pf = 64;
+    b->pf = (uint32_t)env_int("PQUIC_FEC_BATCH_PREFETCH", 8, 0, 64);
     const size_t chunk = (size_t)cfg->batch_blocks * 20 * b->stride / (size_t)cfg->nstreams;
-    const char *ne = getenv("PQUIC_FEC_BATCH_ENGINES");
-    b->nengines = ne && atoi(ne) > 0 ? atoi(ne) : 2;
-    if (b->nengines > MAX_ENGINES) b->nengines = MAX_ENGINES;
+    b->nengines = env_int("PQUIC_FEC_BATCH_ENGINES", 2, 1, MAX_ENGINES);
     for (int e = 0; e < b->nengines; e++) {
         b->ctx[e] = fecgpu_host_ctx_create(cfg->device, cfg->nstreams, chunk < (1u << 20) ? (1u << 20) : chunk);
         if (!b->ctx[e]) {
@@ -849,11 +849,9 @@ pquic_fec_batcher_t *pquic_fec_batcher_create(const pquic_fec_batch_cfg_t *cfg) 
     pthread_cond_init(&b->cv_done, NULL);
     pthread_cond_init(&b->cv_prov, NULL);
     /* copy threads: half the CPUs of the process's share (the caller and the engine thread keep the
-     * rest), at least 2; PQUIC_FEC_BATCH_STAGERS overrides, read once per batcher */
-    const char *ns = getenv("PQUIC_FEC_BATCH_STAGERS");
+     * rest), at least 2; PQUIC_FEC_BATCH_STAGERS overrides */
     const int half = host_cpus() / 2;
-    b->nstagers = ns && atoi(ns) > 0 ? atoi(ns) : (half > 2 ? half : 2);
-    if (b->nstagers > MAX_STAGERS) b->nstagers = MAX_STAGERS;
+    b->nstagers = env_int("PQUIC_FEC_BATCH_STAGERS", half > 2 ? half : 2, 1, MAX_STAGERS);
     int started = 0;
     cpu_set_t near;
     local_cpus(cfg->device, &near);
@@ -887,16 +885,9 @@ pquic_fec_batcher_t *pquic_fec_batcher_create(const pquic_fec_batch_cfg_t *cfg) 
         free(b);
         return NULL;
     }
-    /* the provisioner (spare jobs); without it every job is allocated on the caller's thread.
-     * PQUIC_FEC_BATCH_SPARES=0 turns it off (A/B), read once per batcher like the thread counts */
-    const char *sp = getenv("PQUIC_FEC_BATCH_SPARES");
-    b->prov_started = !(sp && atoi(sp) == 0) && pthread_create(&b->prov, NULL, prov_main, b) == 0;
-    const char *rs = getenv("PQUIC_FEC_BATCH_RESERVE");  /* idle jobs per shape the provisioner keeps (A/B) */
-    b->reserve = rs && atoi(rs) > 0 ? (atoi(rs) < 8 ? atoi(rs) : 8) : 1;
-    const char *sm = getenv("PQUIC_FEC_BATCH_SMALL");  /* 0: the caller allocates full-size jobs (A/B) */
-    b->small_cap = cfg->batch_blocks >= 1024 && !(sm && atoi(sm) == 0) ? cfg->batch_blocks / 16 : 0;
-    const char *ho = getenv("PQUIC_FEC_BATCH_HOLD");
-    b->hold = !(ho && atoi(ho) == 0);
+    /* the provisioner (spare jobs); should its thread not start, every job is allocated on the caller's thread */
+    b->prov_started = pthread_create(&b->prov, NULL, prov_main, b) == 0;
+    b->small_cap = cfg->batch_blocks >= 1024 ? cfg->batch_blocks / 16 : 0;
     return b;
 }
 
@@ -1191,7 +1182,7 @@ static int collect(pquic_fec_batcher_t *b, uint32_t budget) {
  * keeps filling instead, up to its capacity, and is flushed at the first poll that has a job back; the
  * provisioner is asked for one meanwhile. */
 static int deadline_hold(pquic_fec_batcher_t *b, const job_t *j) {
-    if (!b->hold || !b->prov_started || b->next_seq - b->jobs_back < 2) return 0;
+    if (!b->prov_started || b->next_seq - b->jobs_back < 2) return 0;
     const uint32_t cap = b->cfg.batch_blocks, S = j->op == OP_WINDOW ? window_stride(b) : b->stride;
     const size_t sb = (size_t)cap * j->k * S, rb = (size_t)cap * j->r * S;
     const uint32_t sm = j->op == OP_WINDOW ? 0 : b->small_cap;

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <limits.h>
 #include <time.h>
 #include <atomic>
 #include <mutex>
@@ -47,85 +48,94 @@ using namespace fecdev;
 #define FECGPU_VERSION "pquic_amd fecgpu 0.2 (gfx950, bitsliced GF(256) data path)"
 
 static thread_local char g_err[256];
-static std::atomic<uint64_t> g_stats[4];
+static std::atomic<uint64_t> g_stats[4];  // encode calls, encode blocks, decode calls, decode blocks
+static inline void count_encode(uint64_t nblocks) { g_stats[0]++; g_stats[1] += nblocks; }
+static inline void count_decode(uint64_t nblocks) { g_stats[2]++; g_stats[3] += nblocks; }
 
 // ---------------------------------------------------------------------------------------------
 // Experiment knobs (A/B runs; the tests cross-check alternative kernels).  The defaults are the
-// measured best, and only fecgpu_set_knob changes one (include/fecgpu.h): the library reads no
+// measured best, and only fecgpu_set_knob changes one (include/fecgpu.h): the engine reads no
 // environment variables, so nothing outside the caller's own calls can change which kernels run.
+// One row per knob: name, default, and the values fecgpu_set_knob accepts -- [lo, hi], or the set a
+// predicate names (a tile of 3 repairs would dispatch a 16-repair body while stepping r0 by 3).
 // ---------------------------------------------------------------------------------------------
-enum KnobId { K_PLAN, K_INTERLEAVE, K_GROUP, K_ENC_RT, K_ENC_W, K_ZC_READ, K_RING, K_WINDOW_SC, K_MIN_GROUPS,
-              K_ENC_BW,
-              K_CHUNK_WAVES, K_SMALL_LDS, K_BLOCK_SVC, K_WS_LDS, K_DEC_WAVES, K_YIELD_SLICE_KB, K_YIELD_DEPTH,
-              K_YIELD_GATE_US, K_YIELD_STREAMS, K_YIELD_ALWAYS, K_YIELD_WINDOW_MS, K_SVC_RESERVE_CUS, K_HOST_ALLOC, K_ZC_CUS, K_N };
-static const char *const kKnobName[K_N] = {"plan", "interleave", "group", "enc_tile_rt", "enc_tile_waves",
-                                           "zc_read", "ring", "window_sc", "min_groups", "enc_block_waves", "chunk_waves",
-                                           "small_lds", "block_svc", "ws_lds", "dec_waves", "yield_slice_kb",
-                                           "yield_depth", "yield_gate_us", "yield_streams", "yield_always",
-                                           "yield_window_ms", "svc_reserve_cus", "host_alloc", "zc_cus"};
 enum { PLAN_AUTO = 0, PLAN_WAVE = 1, PLAN_LANE = 2, PLAN_REG = 3, PLAN_TILE = 4, PLAN_WREG = 5 };
+static bool enc_tile_rt_ok(int v) { return v == 0 || v == 1 || v == 2 || v == 4 || v == 8 || v == 16; }
+static bool enc_block_waves_ok(int v) { return v == 1 || v == 2 || v == 4; }
+static bool ring_ok(int v) { return v == 0 || v == 2; }
+
+#define FEC_KNOBS(X)                                                                                            \
+  /* plan kernel: 0 by batch size and shape, else PLAN_* forces one (the tests compare them) */                \
+  X(PLAN, "plan", PLAN_AUTO, PLAN_AUTO, PLAN_WREG, nullptr)                                                     \
+  /* bit 0: interleaved block groups; bit 1: XCD-aware group order (grp_index) */                              \
+  X(INTERLEAVE, "interleave", 1, 0, 3, nullptr)                                                                 \
+  /* 0: the measured per-shape group sizes; n: a plain cap on blocks per group */                              \
+  X(GROUP, "group", 0, 0, INT_MAX, nullptr)                                                                     \
+  /* encode tiles by r (0) or of this many repairs, one wave per group (enc_tile_waves 0) or more */           \
+  X(ENC_RT, "enc_tile_rt", 0, 0, 16, enc_tile_rt_ok)                                                            \
+  X(ENC_W, "enc_tile_waves", 0, 0, 4, nullptr)                                                                  \
+  /* register-prefetch encode: waves per workgroup, each on its own block group (adjacent groups share a CU;  \
+     §5.6 probe acol); 1 = one wave per workgroup */                                                           \
+  X(ENC_BW, "enc_block_waves", 1, 1, 4, enc_block_waves_ok)                                                     \
+  /* page-locked host buffers read by the kernels in place (1) or staged by copies (0) */                      \
+  X(ZC_READ, "zc_read", 1, 0, 1, nullptr)                                                                       \
+  /* LDS-ring data path (bs2 bodies) for 16-repair / 16-unknown tiles: 2 on, 0 off */                          \
+  X(RING, "ring", 2, 0, 2, ring_ok)                                                                             \
+  /* window encode on the shared-coefficient kernel (k_rlc_encode_sc): 0 never, 1 for overlapping windows,    \
+     2 wherever it applies (tests) */                                                                          \
+  X(WINDOW_SC, "window_sc", 1, 0, 2, nullptr)                                                                   \
+  /* batches too small to fill the chip stream fewer blocks per wave: groups of blocks shrink until there     \
+     are at least this many groups (0: the per-shape group sizes at every batch size) */                       \
+  X(MIN_GROUPS, "min_groups", 1024, 0, INT_MAX, nullptr)                                                        \
+  /* ring tiles of symbols wider than one column chunk: one wave per chunk of a block at once (1) or one      \
+     wave coding the chunks in turn (0) */                                                                     \
+  X(CHUNK_WAVES, "chunk_waves", 1, 0, 1, nullptr)                                                               \
+  /* batches of <= kSmallLdsMaxBlocks blocks: rows staged in LDS by a workgroup per block (1) or the          \
+     bitsliced one-wave-per-block kernels (0) */                                                               \
+  X(SMALL_LDS, "small_lds", 1, 0, 1, nullptr)                                                                   \
+  /* fecgpu_block_svc_*: the resident worker serves requests (1) or every call returns FECGPU_ERR_INVALID so  \
+     the caller takes the launch path (0) */                                                                   \
+  X(BLOCK_SVC, "block_svc", 1, 0, 1, nullptr)                                                                   \
+  /* recover data pass: a group's workspace records copied into LDS in one round trip (1) or read where they  \
+     lie during the setup (0) */                                                                               \
+  X(WS_LDS, "ws_lds", 1, 0, 1, nullptr)                                                                         \
+  /* recover data pass (register-prefetch bodies): 0 = the occupancy its registers allow, n = at most n       \
+     waves per SIMD */                                                                                         \
+  X(DEC_WAVES, "dec_waves", 0, 0, 8, nullptr)                                                                   \
+  /* zero-copy bulk calls while the hooks are in use (host_path.hip, Pacer): slices of this many KiB of       \
+     payload (0: never slice), at most yield_depth in flight, alternating over yield_streams of the           \
+     context's streams, and a slice held back at most yield_gate_us while a hook request is pending (0: not   \
+     held).  Beside back-to-back 4096-block zero-copy encodes (profiles/r05_pacer_sweep.log): 2560 KiB, 16,   \
+     2 streams -> hooks p99 174 / 184 us (generate / recover; unsliced 1473 / 1486) for bulk calls 9 % longer \
+     (1.725 against 1.582 ms); 2048 KiB -> p99 142-152 us, +12 %; 3072 KiB -> 207-218 us, +7 %.  2304 KiB     \
+     (profiles/r05_pacer_sweep2.log, one box, twice): p99 158 / 170 us against 2560's 175 / 187 for bulk      \
+     calls 0.9 % longer -- the margin under 200 us the bench's runs needed (one read recover p99 202) */       \
+  X(YIELD_SLICE_KB, "yield_slice_kb", 2304, 0, 1 << 20, nullptr)                                                \
+  X(YIELD_DEPTH, "yield_depth", 16, 1, 16, nullptr)                                                             \
+  X(YIELD_GATE_US, "yield_gate_us", 0, 0, 10000, nullptr)                                                       \
+  X(YIELD_STREAMS, "yield_streams", 2, 1, 4, nullptr)                                                           \
+  /* A/B: slice even when no hook has run lately */                                                            \
+  X(YIELD_ALWAYS, "yield_always", 0, 0, 1, nullptr)                                                             \
+  /* the hooks count as in use for this long after a request (tests lengthen it so that slicing does not      \
+     depend on how quickly the call follows the hook) */                                                       \
+  X(YIELD_WINDOW_MS, "yield_window_ms", 100, 0, 600000, nullptr)
+
+#define X(id, name, def, lo, hi, ok) K_##id,
+enum KnobId { FEC_KNOBS(X) K_N };
+#undef X
+struct KnobRow {
+  const char *name;
+  int def, lo, hi;
+  bool (*ok)(int);  // set-valued knobs: the members within [lo, hi]
+};
+#define X(id, name, def, lo, hi, ok) {name, def, lo, hi, ok},
+static const KnobRow kKnobs[K_N] = {FEC_KNOBS(X)};
+#undef X
 static std::atomic<int> g_knob[K_N];
 static std::once_flag g_knob_once;
 
 static void knobs_default() {
-  g_knob[K_PLAN] = PLAN_AUTO;  // plan kernel by batch size and shape
-  g_knob[K_INTERLEAVE] = 1;    // bit 0: interleaved block groups; bit 1: XCD-aware group order (grp_index)
-  g_knob[K_GROUP] = 0;         // 0: the measured per-shape group sizes
-  g_knob[K_ENC_RT] = 0;        // encode tiles by r (0), one wave per group (enc_tile_waves 0)
-  g_knob[K_ENC_W] = 0;
-  // register-prefetch encode: waves per workgroup, each on its own block group (adjacent groups share a CU;
-  // §5.6 probe acol); 1 = one wave per workgroup
-  g_knob[K_ENC_BW] = 1;
-  g_knob[K_ZC_READ] = 1;       // page-locked host buffers read by the kernels in place
-  // LDS-ring data path (bs2 bodies) for 16-repair / 16-unknown tiles: 2 (default) on, 0 off
-  g_knob[K_RING] = 2;
-  // window encode on the shared-coefficient kernel (k_rlc_encode_sc): 0 never, 1 (default) for
-  // overlapping windows, 2 wherever it applies (tests)
-  g_knob[K_WINDOW_SC] = 1;
-  // batches too small to fill the chip stream fewer blocks per wave: groups of blocks shrink until
-  // there are at least this many groups (0: the per-shape group sizes at every batch size)
-  g_knob[K_MIN_GROUPS] = 1024;
-  // ring tiles of symbols wider than one column chunk: one wave per chunk of a block at once (1) or
-  // one wave coding the chunks in turn (0)
-  g_knob[K_CHUNK_WAVES] = 1;
-  // batches of <= kSmallLdsMaxBlocks blocks: rows staged in LDS by a workgroup per block (1) or the
-  // bitsliced one-wave-per-block kernels (0)
-  g_knob[K_SMALL_LDS] = 1;
-  // fecgpu_block_svc_*: the resident worker serves requests (1) or every call returns
-  // FECGPU_ERR_INVALID so the caller takes the launch path (0)
-  g_knob[K_BLOCK_SVC] = 1;
-  // recover data pass: a group's workspace records copied into LDS in one round trip (1) or read
-  // where they lie during the setup (0)
-  g_knob[K_WS_LDS] = 1;
-  // recover data pass (register-prefetch bodies): 0 = the occupancy its registers allow, n = at most
-  // n waves per SIMD
-  g_knob[K_DEC_WAVES] = 0;
-  // zero-copy bulk calls while the hooks are in use (host_path.hip, Pacer): slices of this many KiB of
-  // payload (0: never slice), at most yield_depth in flight, alternating over yield_streams of the
-  // context's streams, and a slice held back at most yield_gate_us while a hook request is pending (0:
-  // not held).  Beside back-to-back 4096-block zero-copy encodes (profiles/r05_pacer_sweep.log): 2560 KiB,
-  // 16, 2 streams -> hooks p99 174 / 184 us (generate / recover; unsliced 1473 / 1486) for bulk calls
-  // 9 % longer (1.725 against 1.582 ms); 2048 KiB -> p99 142-152 us, +12 %; 3072 KiB -> 207-218 us, +7 %.
-  // 2304 KiB (profiles/r05_pacer_sweep2.log, one box, twice): p99 158 / 170 us against 2560's 175 / 187 for
-  // bulk calls 0.9 % longer -- the margin under 200 us the bench's runs needed (one read recover p99 202)
-  g_knob[K_YIELD_SLICE_KB] = 2304;
-  g_knob[K_YIELD_DEPTH] = 16;
-  g_knob[K_YIELD_GATE_US] = 0;
-  g_knob[K_YIELD_STREAMS] = 2;
-  g_knob[K_YIELD_ALWAYS] = 0;   // A/B: slice even when no hook has run lately
-  // the hooks count as in use for this long after a request (tests lengthen it so that slicing does
-  // not depend on how quickly the call follows the hook)
-  g_knob[K_YIELD_WINDOW_MS] = 100;
-  // CUs kept for the block service's worker (0: none): its stream runs on the last n CUs only and the
-  // host-path contexts' streams (the zero-copy bulk calls) on the others; read when a service or a
-  // context is created
-  g_knob[K_SVC_RESERVE_CUS] = 0;
-  // fecgpu_host_alloc's page-locked memory: 0 the runtime's default, 1 fine-grained (coherent), 2
-  // coarse-grained (non-coherent), mapped either way (A/B of how zero-copy kernels' host lines sit in L2)
-  g_knob[K_HOST_ALLOC] = 0;
-  // host-path context streams on only n CUs spread over the chip (0: all): caps how many waves a zero-copy
-  // bulk call keeps reading host memory at once (A/B of the hooks' wait behind it)
-  g_knob[K_ZC_CUS] = 0;
+  for (int i = 0; i < K_N; i++) g_knob[i] = kKnobs[i].def;
 }
 
 static inline int knob(KnobId id) {
@@ -133,10 +143,9 @@ static inline int knob(KnobId id) {
   return g_knob[id].load(std::memory_order_relaxed);
 }
 
-// host_path.hip reads the zero-copy knob through this (library-internal)
+// host_path.hip reads its knobs through these (library-internal)
 extern "C" __attribute__((visibility("hidden"))) int fecgpu_knob_zc_read(void) { return knob(K_ZC_READ); }
 extern "C" __attribute__((visibility("hidden"))) int fecgpu_knob_window_sc(void) { return knob(K_WINDOW_SC); }
-extern "C" __attribute__((visibility("hidden"))) int fecgpu_knob_host_alloc(void) { return knob(K_HOST_ALLOC); }
 extern "C" __attribute__((visibility("hidden"))) void fecgpu_knob_yield(int *slice_kb, int *depth, int *gate_us,
                                                                         int *streams, int *always, int *window_ms) {
   *slice_kb = knob(K_YIELD_SLICE_KB);
@@ -145,33 +154,6 @@ extern "C" __attribute__((visibility("hidden"))) void fecgpu_knob_yield(int *sli
   *gate_us = knob(K_YIELD_GATE_US);
   *streams = knob(K_YIELD_STREAMS);
   *always = knob(K_YIELD_ALWAYS);
-}
-
-// CU masks of the block-service reservation (knob svc_reserve_cus = n): worker = 1 gives the last n CUs,
-// worker = 0 every other CU.  Returns the mask's words (0: no reservation; the caller makes a plain stream).
-extern "C" __attribute__((visibility("hidden"))) int fecgpu_svc_cu_mask(int device, int worker, uint32_t *mask,
-                                                                        int max_words) {
-  // n > 0: the last n CU indices; n < 0: every (-n)-th CU index counted from the last (-8: the indices
-  // c % 8 == 7, one XCD's CUs where the queue's CU numbering interleaves the eight XCDs)
-  const int n = knob(K_SVC_RESERVE_CUS), zc = knob(K_ZC_CUS);
-  int cus = 0;
-  if ((n == 0 && (zc == 0 || worker)) ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
-      cus <= (n > 0 ? n : -n) || (cus + 31) / 32 > max_words)
-    return 0;
-  const int words = (cus + 31) / 32;
-  for (int w = 0; w < words; w++) mask[w] = 0;
-  if (!worker && zc > 0 && zc < cus) {  // zc_cus: the host-path streams on zc CUs, every (cus / zc)-th index
-    const int step = cus / zc;
-    for (int c = 0, m = 0; c < cus && m < zc; c += step, m++) mask[c >> 5] |= 1u << (c & 31);
-    return words;
-  }
-  if (n == 0) return 0;
-  for (int c = 0; c < cus; c++) {
-    const bool reserved = n > 0 ? c >= cus - n : (c % -n) == (-n - 1);
-    if (reserved == (worker != 0)) mask[c >> 5] |= 1u << (c & 31);
-  }
-  return words;
 }
 
 static int set_err(int code, const char *fmt, const char *what) {
@@ -1610,7 +1592,7 @@ __device__ __forceinline__ void bs_dec_call(uint32_t ia, uint32_t oa, uint32_t n
 // - symbols wider than one column chunk (L > 2 KiB): one block per group (k64 r16 L9000 encode
 //   -2.3 %, decode -8.3 %: the chunk passes then revisit one block's rows);
 // - everything else: 64 / RT.
-// Knob "group" (FECGPU_GROUP=N) replaces the defaults with a plain cap (A/B experiments).
+// Knob "group" = N replaces the defaults with a plain cap (A/B experiments).
 // - batches of fewer than min_groups (default 1024, one wave per SIMD) groups: halved until there
 //   are that many groups or one block per group.  A group is streamed by one wave, so a batch of 8
 //   k32 r8 blocks took 137 us in one group against 22 us for one block
@@ -1634,7 +1616,7 @@ static inline int bs_group(int RT, int k, int per_j_bytes, int per_block_bytes, 
 
 // W waves per workgroup can split the repairs of one group of blocks: wave w owns repairs
 // r0 + w*RT .. +RT, streaming the same source rows close together in time (L2 serves the
-// repeats).  Default W = 1 (see pick_enc_tile); W > 1 is kept for FECGPU_ENC_TILE experiments.
+// repeats).  Default W = 1 (see pick_enc_tile); W > 1 is kept for enc_tile_waves experiments.
 #ifndef FEC_V1_ENC8_WAVES
 #define FEC_V1_ENC8_WAVES 1  // set by bitslice_gen.h when 8-repair encode tiles use the compact register map
 #endif
@@ -2402,7 +2384,7 @@ static BsCfg pick_bs_cfg(int L) {
 // sliding window's step * L, where consecutive blocks overlap).  The asm streams a group's
 // sources as one run of contiguous rows, so overlapping blocks go one per group.
 // Interleaved groups (default): a group's blocks are NG apart, so the resident waves stream
-// neighbouring blocks.  FECGPU_INTERLEAVE=0 restores contiguous groups (A/B experiments).
+// neighbouring blocks.  Knob interleave = 0 restores contiguous groups (A/B experiments).
 static int interleave_groups() { return knob(K_INTERLEAVE); }
 
 template <int RT, int VEC>
@@ -2568,24 +2550,9 @@ static bool launch_encode_sc(const uint8_t *sym, uint8_t *rep, uint64_t nwin, in
 // ---------------------------------------------------------------------------------------------
 #define FEC_BS2_D(MODE, RT) FEC_BS2_D_##MODE##_RT##RT
 
-// ring depths (sources in flight + 1) of the shipped ring bodies: 16-repair / 16-unknown tiles.  A build
-// whose generator also emitted 4-unknown ring bodies (FEC_GEN2_TILES=4,16) can run the 4-unknown
-// recover tiles on the ring as well (knob ring = 4; A/B experiments)
+// ring depths (sources in flight + 1) of the ring bodies: 16-repair / 16-unknown tiles only
 template <int RT> struct Bs2Depth;
 template <> struct Bs2Depth<16> { static constexpr int enc = FEC_BS2_D(ENC, 16), dec = FEC_BS2_D(DEC, 16); };
-#ifdef FEC_BS2_D_DEC_RT4
-#define FEC_BS2_HAS_RT4 1
-template <> struct Bs2Depth<4> { static constexpr int enc = FEC_BS2_D(ENC, 4), dec = FEC_BS2_D(DEC, 4); };
-#else
-#define FEC_BS2_HAS_RT4 0
-#endif
-// 8-repair ring encode bodies (FEC_GEN2_TILES=8,16 builds; knob ring = 8; A/B experiments)
-#ifdef FEC_BS2_D_ENC_RT8
-#define FEC_BS2_HAS_RT8 1
-template <> struct Bs2Depth<8> { static constexpr int enc = FEC_BS2_D(ENC, 8), dec = FEC_BS2_D(DEC, 8); };
-#else
-#define FEC_BS2_HAS_RT8 0
-#endif
 using Bs2Depth16 = Bs2Depth<16>;
 
 // Lane geometry of one chunk of cb bytes (cb >= 16) as 16-B pieces, the last pulled back to end at cb.
@@ -2641,24 +2608,12 @@ template <int RT>
 __device__ __forceinline__ void bs2_enc_call(bool two, uint64_t sp, uint64_t rpp, int L, uint32_t rslo, uint32_t rshi,
                                              uint64_t sdl, uint64_t ll, int rt, uint32_t nsrc, int k, uint32_t ca,
                                              uint32_t ring, const Bs2Lanes &ln) {
-#if FEC_BS2_HAS_RT8
-  if constexpr (RT == 8) {
-    if (two) BS2_CALL_ENC(8, 2); else BS2_CALL_ENC(8, 1);
-    return;
-  }
-#endif
   if (two) BS2_CALL_ENC(16, 2); else BS2_CALL_ENC(16, 1);
 }
 
 template <int RT>
 __device__ __forceinline__ void bs2_dec_call(bool two, uint32_t ia, uint32_t oa, uint32_t nsrc, int k, uint32_t ca,
                                              uint32_t ring, const Bs2Lanes &ln) {
-#if FEC_BS2_HAS_RT4
-  if constexpr (RT == 4) {
-    if (two) BS2_CALL_DEC(4, 2); else BS2_CALL_DEC(4, 1);
-    return;
-  }
-#endif
   if (two) BS2_CALL_DEC(16, 2); else BS2_CALL_DEC(16, 1);
 }
 
@@ -2977,29 +2932,9 @@ static void launch_recover_bs2(uint8_t *src, const uint8_t *rep, uint64_t nb, in
 // of at least D sources (one epilogue in any wait window, see gen_bitslice.py body2); knob ring = 0
 // keeps those tiles on the register-prefetch body (A/B).
 static bool use_ring(int rt, uint32_t k, const BsCfg &cfg, bool enc) {
-  if (knob(K_RING) == 0 || cfg.vec != 16) return false;
-  if (rt == 16) return (int)k >= (enc ? Bs2Depth16::enc : Bs2Depth16::dec);
-#if FEC_BS2_HAS_RT8
-  if (rt == 8 && enc && knob(K_RING) == 8) return (int)k >= Bs2Depth<8>::enc;
-#endif
-#if FEC_BS2_HAS_RT4
-  if (rt == 4 && !enc && knob(K_RING) == 4) return (int)k >= Bs2Depth<4>::dec;
-#endif
-  return false;
+  if (knob(K_RING) == 0 || cfg.vec != 16 || rt != 16) return false;
+  return (int)k >= (enc ? Bs2Depth16::enc : Bs2Depth16::dec);
 }
-
-#if FEC_BS2_HAS_RT4
-#define FEC_BS2_DISPATCH_DEC(FN, ...) \
-  if (rt == 4) FN<4>(__VA_ARGS__); else FN<16>(__VA_ARGS__);
-#else
-#define FEC_BS2_DISPATCH_DEC(FN, ...) FN<16>(__VA_ARGS__);
-#endif
-#if FEC_BS2_HAS_RT8
-#define FEC_BS2_DISPATCH(FN, ...) \
-  if (rt == 8) FN<8>(__VA_ARGS__); else FN<16>(__VA_ARGS__);
-#else
-#define FEC_BS2_DISPATCH(FN, ...) FN<16>(__VA_ARGS__);
-#endif
 
 #define FEC_BS_DISPATCH(FN, ...)                                                   \
   switch (rt * 100 + cfg.vec) {                                                    \
@@ -3037,6 +2972,19 @@ static int bs_table_check() {
     g_tab_state[dev].store(st);
   }
   if (st < 0) return set_err(FECGPU_ERR_HIP, "%s", "GF(256) case table is not 64 KiB-aligned in device memory");
+  return FECGPU_OK;
+}
+
+// A kernel launched with more than the default 64 KiB of dynamic LDS has its limit raised to the CU's
+// 160 KiB first, once per device (`raised`: the kernel's own per-device flags).
+static int raise_lds_limit(const void *kernel, std::atomic<bool> (&raised)[64]) {
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return set_err(FECGPU_ERR_NO_DEVICE, "%s", "device index out of range");
+  if (!raised[dev].load()) {
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    raised[dev].store(true);
+  }
   return FECGPU_OK;
 }
 
@@ -3280,6 +3228,8 @@ __global__ void k_synth_fill(uint8_t *dst, uint64_t nbytes, uint64_t seed, uint6
 // Launch configuration
 // =============================================================================================
 static int pick_rt(uint32_t r) { return r >= 16 ? 16 : r >= 8 ? 8 : r >= 4 ? 4 : r >= 2 ? 2 : 1; }
+// decode passes: the smallest tile covering e_max (one pass, finalize fused), up to 16 unknowns
+static int decode_tile(uint32_t em) { return em <= 1 ? 1 : em <= 2 ? 2 : em <= 4 ? 4 : em <= 8 ? 8 : 16; }
 
 static uint32_t grid_for(uint64_t units) {
   const uint64_t cap = 1u << 22;
@@ -3322,51 +3272,28 @@ int fecgpu_init(int device) {
   return rc;
 }
 
-// The values each knob accepts: a tile of 3 repairs would
-// dispatch a 16-repair body while stepping r0 by 3, a negative group cap would become a huge
-// unsigned one.
-static bool knob_value_ok(int id, int v) {
-  switch (id) {
-    case K_PLAN: return v >= PLAN_AUTO && v <= PLAN_WREG;
-    case K_ENC_RT: return v == 0 || v == 1 || v == 2 || v == 4 || v == 8 || v == 16;
-    case K_ENC_W: return v >= 0 && v <= 4;
-    case K_ENC_BW: return v == 1 || v == 2 || v == 4;
-    case K_RING: return v == 0 || v == 2 || (v == 4 && FEC_BS2_HAS_RT4) || (v == 8 && FEC_BS2_HAS_RT8);
-    case K_WINDOW_SC: return v >= 0 && v <= 2;
-    case K_GROUP: case K_MIN_GROUPS: return v >= 0;
-    case K_DEC_WAVES: return v >= 0 && v <= 8;
-    case K_YIELD_SLICE_KB: return v >= 0 && v <= (1 << 20);
-    case K_YIELD_DEPTH: return v >= 1 && v <= 16;
-    case K_YIELD_GATE_US: return v >= 0 && v <= 10000;
-    case K_YIELD_STREAMS: return v >= 1 && v <= 4;
-    case K_YIELD_WINDOW_MS: return v >= 0 && v <= 600000;
-    case K_SVC_RESERVE_CUS: return v >= -64 && v <= 128;
-    case K_HOST_ALLOC: return v >= 0 && v <= 2;
-    case K_ZC_CUS: return v >= 0 && v <= 256;
-    case K_INTERLEAVE: return v >= 0 && v <= 3;
-    default: return v == 0 || v == 1;  // on / off knobs
-  }
+static int knob_index(const char *name) {
+  for (int i = 0; name && i < K_N; i++)
+    if (!strcmp(name, kKnobs[i].name)) return i;
+  return -1;
 }
 
 int fecgpu_set_knob(const char *name, int value) {
+  const int i = knob_index(name);
+  if (i < 0) return set_err(FECGPU_ERR_INVALID, "unknown knob %s", name ? name : "(null)");
+  const KnobRow &row = kKnobs[i];
+  if (value < row.lo || value > row.hi || (row.ok && !row.ok(value)))
+    return set_err(FECGPU_ERR_INVALID, "value out of range for knob %s", name);
   std::call_once(g_knob_once, knobs_default);
-  for (int i = 0; i < K_N; i++)
-    if (name && !strcmp(name, kKnobName[i])) {
-      if (!knob_value_ok(i, value)) return set_err(FECGPU_ERR_INVALID, "value out of range for knob %s", name);
-      g_knob[i].store(value, std::memory_order_relaxed);
-      return FECGPU_OK;
-    }
-  return set_err(FECGPU_ERR_INVALID, "unknown knob %s", name ? name : "(null)");
+  g_knob[i].store(value, std::memory_order_relaxed);
+  return FECGPU_OK;
 }
 
 int fecgpu_get_knob(const char *name, int *value) {
-  std::call_once(g_knob_once, knobs_default);
-  for (int i = 0; i < K_N; i++)
-    if (name && value && !strcmp(name, kKnobName[i])) {
-      *value = g_knob[i].load(std::memory_order_relaxed);
-      return FECGPU_OK;
-    }
-  return set_err(FECGPU_ERR_INVALID, "unknown knob %s", name ? name : "(null)");
+  const int i = value ? knob_index(name) : -1;
+  if (i < 0) return set_err(FECGPU_ERR_INVALID, "unknown knob %s", name ? name : "(null)");
+  *value = knob((KnobId)i);
+  return FECGPU_OK;
 }
 
 #ifdef FEC_STAMP
@@ -3390,10 +3317,10 @@ void fecgpu_get_stats(fecgpu_stats_t *out) {
 }
 
 // Encode tiling: repairs per wave (RT) and waves per workgroup sharing the source stream.
-// Knobs enc_tile_rt / enc_tile_waves (FECGPU_ENC_TILE="RT,W") override (A/B experiments).
+// Knobs enc_tile_rt / enc_tile_waves override (A/B experiments).
 struct EncTile { int rt, waves; };
 static EncTile pick_enc_tile(uint32_t r) {
-  if (const int a = knob(K_ENC_RT)) {  // knobs enc_tile_rt / enc_tile_waves (FECGPU_ENC_TILE="RT,W")
+  if (const int a = knob(K_ENC_RT)) {
     const int b = knob(K_ENC_W);
     return {a, b >= 1 && b <= 4 ? b : 1};
   }
@@ -3422,8 +3349,7 @@ int fecgpu_rlc_encode(const void *src, void *rep, uint64_t nblocks, uint32_t k, 
         hipLaunchKernelGGL(k_rlc_encode_lds<16>, dim3(grid), dim3(kLdsThreads), Y.bytes, s, (const uint8_t *)src,
                            (uint8_t *)rep, nblocks, (int)k, (int)r, (int)symbol_size, fbn_base, fbn);
       HIPCHK(hipGetLastError());
-      g_stats[0]++;
-      g_stats[1] += nblocks;
+      count_encode(nblocks);
       return FECGPU_OK;
     }
   }
@@ -3433,8 +3359,8 @@ int fecgpu_rlc_encode(const void *src, void *rep, uint64_t nblocks, uint32_t k, 
   const int rt = et.rt;
   if (use_ring(rt, k, cfg, true)) {
     for (int r0 = 0; r0 < (int)r; r0 += rt * et.waves) {
-      FEC_BS2_DISPATCH(launch_encode_bs2, (const uint8_t *)src, (uint8_t *)rep, nblocks, (int)k, (int)r,
-                       (int)symbol_size, cfg, fbn_base, fbn, r0, et.waves, (uint64_t)k * symbol_size, 1u, s)
+      launch_encode_bs2<16>((const uint8_t *)src, (uint8_t *)rep, nblocks, (int)k, (int)r, (int)symbol_size, cfg,
+                            fbn_base, fbn, r0, et.waves, (uint64_t)k * symbol_size, 1u, s);
     }
   } else {
     for (int r0 = 0; r0 < (int)r; r0 += et.rt * et.waves) {
@@ -3443,8 +3369,7 @@ int fecgpu_rlc_encode(const void *src, void *rep, uint64_t nblocks, uint32_t k, 
     }
   }
   HIPCHK(hipGetLastError());
-  g_stats[0]++;
-  g_stats[1] += nblocks;
+  count_encode(nblocks);
   return FECGPU_OK;
 }
 
@@ -3461,8 +3386,7 @@ int fecgpu_rlc_encode_rows(const uint64_t *src_rows, const uint64_t *rep_rows, u
                     fbn, r0, s)
   }
   HIPCHK(hipGetLastError());
-  g_stats[0]++;
-  g_stats[1] += nblocks;
+  count_encode(nblocks);
   return FECGPU_OK;
 }
 
@@ -3483,8 +3407,7 @@ int fecgpu_rlc_window_encode(const void *symbols, uint64_t nwindows, uint32_t st
     }
   }
   HIPCHK(hipGetLastError());
-  g_stats[0]++;
-  g_stats[1] += nwindows;
+  count_encode(nwindows);
   return FECGPU_OK;
 }
 
@@ -3500,8 +3423,7 @@ int fecgpu_rlc_window_encode_table(const void *symbols, uint64_t nrows, const ui
                         (hipStream_t)stream, wrow, nrows))
     return set_err(FECGPU_ERR_INVALID, "%s", "window table encode: stream of 2 GiB or more, or window_sc knob 0");
   HIPCHK(hipGetLastError());
-  g_stats[0]++;
-  g_stats[1] += nwindows;
+  count_encode(nwindows);
   return FECGPU_OK;
 }
 
@@ -3525,8 +3447,7 @@ int fecgpu_xor_encode(const void *src, void *rep, uint64_t nblocks, uint32_t k, 
                                                  (int)k, Lv);
   }
   HIPCHK(hipGetLastError());
-  g_stats[0]++;
-  g_stats[1] += nblocks;
+  count_encode(nblocks);
   return FECGPU_OK;
 }
 
@@ -3560,8 +3481,8 @@ static int decode_plan_impl(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t f
   hipStream_t s = (hipStream_t)stream;
   uint8_t *ws = (uint8_t *)workspace;
   const size_t lane_lds = plan_lane_lds(k, r);
-  // knob "plan" (FECGPU_PLAN=reg|tile|lane|wave) overrides the size rule (A/B experiments; the tests
-  // compare the plan kernels on the same inputs through fecgpu_set_knob)
+  // knob "plan" (1 wave, 2 lane, 3 reg, 4 tile, 5 wave in registers) overrides the size rule (A/B
+  // experiments; the tests compare the plan kernels on the same inputs through fecgpu_set_knob)
   int force = knob(K_PLAN);
   // the wave kernel takes the register plan wherever it fits unless the LDS wave plan is forced
   const int wreg = force != PLAN_WAVE;
@@ -3585,17 +3506,10 @@ static int decode_plan_impl(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t f
     HIPCHK(hipGetLastError());
     return FECGPU_OK;
   }
-  if ((force == 0 || force == 4) && k <= 64 && em <= 16) {  // FECGPU_PLAN=tile
+  if ((force == 0 || force == 4) && k <= 64 && em <= 16) {  // knob plan = 4 (tile)
     constexpr int BPW = 16, EM = 16;  // k_rlc_plan_tile<4, 16>: 4 lanes per block
+    // at most 39 744 B (k = 64, r = 16) under this guard: within the default dynamic-LDS limit
     const size_t tile_lds = 768 + (size_t)BPW * EM * pad16(k) + (size_t)BPW * plan_out_row(ws_layout(k, r).stride);
-    if (tile_lds > 65536) {
-      static bool raised = false;
-      if (!raised) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_rlc_plan_tile<4, 16>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised = true;
-      }
-    }
     const uint64_t groups = (nblocks + BPW - 1) / BPW;
     hipLaunchKernelGGL((k_rlc_plan_tile<4, 16>), dim3(grid_for(groups)), dim3(64), tile_lds, s, nblocks,
                        (int)k, (int)r, fbn_base, fbn, seeds, src_present, rep_present, ws);
@@ -3603,26 +3517,15 @@ static int decode_plan_impl(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t f
     return FECGPU_OK;
   }
   if (force != 1 && (lane_lds <= 64 * 1024 || force == 2) && lane_lds <= 160 * 1024) {
-    if (lane_lds > 65536) {
-      static bool raised = false;
-      if (!raised) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_rlc_plan_lane, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-        raised = true;
-      }
+    if (lane_lds > 65536) {  // only the forced lane plan (knob plan = 2), e.g. k = 64, r = 8: 84 480 B
+      static std::atomic<bool> raised[64];
+      if (int rc2 = raise_lds_limit((const void *)k_rlc_plan_lane, raised)) return rc2;
     }
     const uint64_t groups = (nblocks + 63) / 64;
     hipLaunchKernelGGL(k_rlc_plan_lane, dim3(grid_for(groups)), dim3(64), lane_lds, s, nblocks, (int)k,
                        (int)r, fbn_base, fbn, seeds, src_present, rep_present, ws);
   } else {
-    const size_t plan_lds = plan_lds_bytes(k, r);
-    if (plan_lds > 65536) {
-      static bool raised = false;
-      if (!raised) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_rlc_plan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan_lds));
-        raised = true;
-      }
-    }
+    const size_t plan_lds = plan_lds_bytes(k, r);  // at most 51 600 B (k = r = 128): within the default limit
     if (wreg && em <= 8 && k + em <= 64) {
 #define FEC_PLAN_WREG(EM)                                                                                  \
   hipLaunchKernelGGL((k_rlc_plan_wreg<EM>), dim3(grid_for(nblocks)), dim3(64), plan_lds, s, nblocks, (int)k, \
@@ -3701,12 +3604,10 @@ static int decode_apply_impl(const void *src, const void *rep, void *dst, uint64
   if (rc || nblocks == 0) return rc;
   if (!dst) return set_err(FECGPU_ERR_INVALID, "%s", "NULL output buffer");
   if ((uintptr_t)dst % 4) return set_err(FECGPU_ERR_INVALID, "%s", "output buffer must be 4-byte aligned");
-  g_stats[2]++;  // decode calls / blocks are counted at the data pass (fecgpu_rlc_decode and the staged API)
-  g_stats[3] += nblocks;
+  count_decode(nblocks);  // decode calls / blocks are counted at the data pass (fecgpu_rlc_decode and the staged API)
   uint8_t *ws = (uint8_t *)workspace;
   const WsLayout L = ws_layout(k, r);
-  // decode passes: the smallest tile covering e_max (one pass, finalize fused) up to 16 unknowns
-  const int rt = L.em <= 1 ? 1 : L.em <= 2 ? 2 : L.em <= 4 ? 4 : L.em <= 8 ? 8 : 16;
+  const int rt = decode_tile(L.em);
   if (r == 0) return launch_finalize(nblocks, k, r, status, recovered, ws, s);
   if (int rc2 = bs_table_check()) return rc2;
   const BsCfg cfg = pick_bs_cfg((int)symbol_size);
@@ -3714,9 +3615,9 @@ static int decode_apply_impl(const void *src, const void *rep, void *dst, uint64
   const bool ring = use_ring(rt, k, cfg, false);
   for (int r0 = 0; r0 < (int)L.em; r0 += rt) {
     if (ring) {
-      FEC_BS2_DISPATCH_DEC(launch_recover_bs2, (uint8_t *)src, (const uint8_t *)rep, nblocks, (int)k, (int)r,
-                       (int)symbol_size, cfg, ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s,
-                       (uint8_t *)dst, dst_rows)
+      launch_recover_bs2<16>((uint8_t *)src, (const uint8_t *)rep, nblocks, (int)k, (int)r, (int)symbol_size, cfg,
+                             ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s, (uint8_t *)dst,
+                             dst_rows);
     } else {
       FEC_BS_DISPATCH(launch_recover_bs, (uint8_t *)src, (const uint8_t *)rep, nblocks, (int)k, (int)r,
                       (int)symbol_size, cfg, ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s,
@@ -3761,13 +3662,12 @@ int fecgpu_rlc_decode_rows(const uint64_t *src_rows, const uint64_t *rep_rows, u
   if ((rc = decode_plan_impl(nblocks, k, r, 0, nullptr, rep_seed, src_present, rep_present, workspace,
                              workspace_bytes, s)))
     return rc;
-  g_stats[2]++;
-  g_stats[3] += nblocks;
+  count_decode(nblocks);
   uint8_t *ws = (uint8_t *)workspace;
   const WsLayout WL = ws_layout(k, r);
   if (r == 0) return launch_finalize(nblocks, k, r, status, recovered, ws, s);
   if (int rc2 = bs_table_check()) return rc2;
-  const int rt = WL.em <= 1 ? 1 : WL.em <= 2 ? 2 : WL.em <= 4 ? 4 : WL.em <= 8 ? 8 : 16;
+  const int rt = decode_tile(WL.em);
   const BsCfg cfg = pick_bs_cfg((int)symbol_size);
   const bool fused = (int)WL.em <= rt;
   // the register-prefetch recover pass for every tile size (the LDS-ring pass computes its row
@@ -3822,8 +3722,7 @@ static int decode_impl(const void *src, const void *rep, void *dst, uint64_t nbl
   if (nblocks <= kSmallLdsMaxBlocks && r > 0 && WL.em <= 16 && knob(K_PLAN) == 0 && knob(K_SMALL_LDS)) {
     const DecLdsLayout Y((int)k, (int)r, (int)L, WL.em <= 4 ? 4 : WL.em <= 8 ? 8 : 16);
     if (Y.bytes <= 65536) {
-      g_stats[2]++;
-      g_stats[3] += nblocks;
+      count_decode(nblocks);
       const int wreg = knob(K_PLAN) != PLAN_WAVE;
 #define FEC_DEC_LDS(EM)                                                                                          \
   hipLaunchKernelGGL(k_rlc_decode_lds<EM>, dim3((uint32_t)nblocks), dim3(kLdsThreads), Y.bytes, s, (const uint8_t *)src, \
@@ -3842,11 +3741,10 @@ static int decode_impl(const void *src, const void *rep, void *dst, uint64_t nbl
   if (nblocks <= kDecodeSmallMaxBlocks && r > 0 && WL.em <= 16 && knob(K_PLAN) == 0 &&
       plan_lds_bytes(k, r) <= 65536) {
     const BsCfg cfg = pick_bs_cfg((int)L);
-    const int rt = WL.em <= 1 ? 1 : WL.em <= 2 ? 2 : WL.em <= 4 ? 4 : WL.em <= 8 ? 8 : 16;
+    const int rt = decode_tile(WL.em);
     if (!use_ring(rt, k, cfg, false)) {
       if (int rc2 = bs_table_check()) return rc2;
-      g_stats[2]++;
-      g_stats[3] += nblocks;
+      count_decode(nblocks);
       FEC_BS_DISPATCH(launch_decode_small, (uint8_t *)src, (const uint8_t *)rep, nblocks, (int)k, (int)r, (int)L,
                       cfg, fbn_base, fbn, seeds, sp, rp, (uint8_t *)ws, status, recovered, (uint8_t *)dst, s)
       HIPCHK(hipGetLastError());
@@ -3920,8 +3818,7 @@ static int xor_decode_impl(void *src, const void *rep, void *dst, uint64_t nbloc
                                                  recovered + 2 * b0, dst ? (uint32_t *)dst + ro : (uint32_t *)nullptr);
   }
   HIPCHK(hipGetLastError());
-  g_stats[2]++;
-  g_stats[3] += nblocks;
+  count_decode(nblocks);
   return FECGPU_OK;
 }
 
@@ -4023,10 +3920,7 @@ fecgpu_block_svc_t *fecgpu_block_svc_create(int device) {
   v->device = device;
   int prio_least = 0, prio_greatest = 0;
   if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_greatest = 0;
-  uint32_t cu_mask[16];
-  const int mw = fecgpu_svc_cu_mask(device, 1, cu_mask, 16);
-  bool ok = (mw ? hipExtStreamCreateWithCUMask(&v->stream, (uint32_t)mw, cu_mask)
-                : hipStreamCreateWithPriority(&v->stream, hipStreamNonBlocking, prio_greatest)) == hipSuccess &&
+  bool ok = hipStreamCreateWithPriority(&v->stream, hipStreamNonBlocking, prio_greatest) == hipSuccess &&
             hipEventCreateWithFlags(&v->ev, hipEventDisableTiming) == hipSuccess &&
             // fine-grained (coherent) explicitly: the host's compare-and-swap on req.seq (svc_unpost) and
             // the worker's system-scope claim must be atomic against each other over PCIe
@@ -4197,8 +4091,7 @@ int fecgpu_block_svc_rlc_encode(fecgpu_block_svc_t *v, const void *src, void *re
   const int rc = svc_run(v);
   if (cur != v->device) (void)hipSetDevice(cur);
   if (!rc) {
-    g_stats[0]++;
-    g_stats[1]++;
+    count_encode(1);
   }
   return rc;
 }
@@ -4235,8 +4128,7 @@ int fecgpu_block_svc_rlc_decode_seeded(fecgpu_block_svc_t *v, const void *src, c
     *status = (uint8_t)v->mb->status;
     recovered[0] = v->mb->recovered[0];
     recovered[1] = v->mb->recovered[1];
-    g_stats[2]++;
-    g_stats[3]++;
+    count_decode(1);
   }
   return rc;
 }

@@ -56,8 +56,6 @@ struct fecgpu_host_ctx {
 
 extern "C" {
 
-int fecgpu_svc_cu_mask(int device, int worker, uint32_t *mask, int max_words);  // fec_engine.hip (internal)
-
 fecgpu_host_ctx_t *fecgpu_host_ctx_create(int device, int nstreams, size_t chunk_bytes) {
   if (fecgpu_init(device) != FECGPU_OK) return nullptr;
   if (hipSetDevice(device) != hipSuccess) return nullptr;
@@ -65,11 +63,8 @@ fecgpu_host_ctx_t *fecgpu_host_ctx_create(int device, int nstreams, size_t chunk
   c->device = device;
   c->ns = nstreams < 1 ? 1 : (nstreams > kMaxStreams ? kMaxStreams : nstreams);
   c->chunk_bytes = chunk_bytes ? chunk_bytes : (64u << 20);
-  uint32_t cu_mask[16];
-  const int mw = fecgpu_svc_cu_mask(device, 0, cu_mask, 16);  // off the block service's CUs (if reserved)
   for (int i = 0; i < c->ns; i++) {
-    if ((mw ? hipExtStreamCreateWithCUMask(&c->slot[i].st, (uint32_t)mw, cu_mask)
-            : hipStreamCreateWithFlags(&c->slot[i].st, hipStreamNonBlocking)) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&c->slot[i].st, hipStreamNonBlocking) != hipSuccess) {
       fecgpu_host_ctx_destroy(c);
       return nullptr;
     }
@@ -167,7 +162,7 @@ static uint8_t *mapped_host(const void *p, size_t len) {
 
 // Page-locked host buffers are read (and written) by the kernels directly over PCIe instead of
 // being staged by copies: measured 49.2 -> 51.0 GiB/s encode, 39.2 -> 50.3 GiB/s decode
-// (k16 r4, 2^18 blocks).  Knob zc_read = 0 (FECGPU_ZC_READ=0) restores the staged copies (A/B).
+// (k16 r4, 2^18 blocks).  Knob zc_read = 0 restores the staged copies (A/B).
 int fecgpu_knob_zc_read(void);  // fec_engine.hip (library-internal, C linkage)
 int fecgpu_rlc_decode_to_internal(const void *src, const void *rep, void *dst, uint64_t nblocks, uint32_t k,
                                   uint32_t r, uint32_t L, uint32_t fbn_base, const uint32_t *fbn,
@@ -624,14 +619,9 @@ int fecgpu_xor_decode_host(fecgpu_host_ctx_t *c, void *src, const void *rep, uin
 }  // extern "C"
 
 extern "C" {
-int fecgpu_knob_host_alloc(void);  // fec_engine.hip (library-internal)
-
 void *fecgpu_host_alloc(size_t bytes) {
   void *p = nullptr;
-  const int mode = fecgpu_knob_host_alloc();
-  const unsigned flags = mode == 1 ? hipHostMallocMapped | hipHostMallocCoherent
-                       : mode == 2 ? hipHostMallocMapped | hipHostMallocNonCoherent : hipHostMallocDefault;
-  if (hipHostMalloc(&p, bytes ? bytes : 1, flags) != hipSuccess) return nullptr;
+  if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) return nullptr;
   hipPointerAttribute_t pa;
   if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.devicePointer)
     pinned_add((uintptr_t)p, bytes ? bytes : 1, (uint8_t *)pa.devicePointer, false);
