@@ -17,7 +17,8 @@
  *   rep  [nblocks][r][symbol_size]   repair symbols
  * Equal-length symbols; symbol_size % 4 == 0 (callers with ragged payloads zero-pad to a
  * common length, which is what the reference does internally: every symbol of a block is
- * treated as zero-padded to max(data_length)).
+ * treated as zero-padded to max(data_length)).  The *_rows_len entry points ("Ragged rows" below)
+ * take a length per row instead and do that padding on the device.
  * FEC block number of block b: fbn[b] if fbn != NULL, else (fbn_base + b) mod 2^24.
  * RLC coefficients of repair i of block fbn come from TinyMT32 seeded with
  * (fbn << 8) | i, exactly as the reference (fec.h:44-75).
@@ -105,6 +106,62 @@ int fecgpu_rlc_decode_rows(const uint64_t *src_rows, const uint64_t *rep_rows, u
                            uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed, const uint64_t *src_present,
                            const uint64_t *rep_present, uint8_t *status, uint64_t *recovered, void *workspace,
                            size_t workspace_bytes, void *stream);
+
+/* ---- Ragged rows: symbols of their own length, coded where they lie ------------------------------
+ * The reference codes symbols of different lengths: generate reads every source for its own
+ * data_length and allocates repairs of the block's max_length (rlc_fec_scheme_generate_gf256.c:41-66);
+ * recover takes max_length from the first present repair, reads every received symbol for its own
+ * length and allocates recovered sources of max_length (rlc_fec_scheme_gf256.c:186-228).  The entry
+ * points below take a length per row beside its address, so a caller pads nothing.
+ *
+ * fecgpu_rows_gather: row x of the table is copied to dst + x * symbol_size -- len[x] bytes, then zeros
+ * up to symbol_size.  fecgpu_rows_scatter: len[x] bytes of packed row x (src + x * symbol_size) go to
+ * the row's address, and not one byte more (16-B and dword stores, byte stores for the last 1-3 bytes;
+ * no dword is read-modify-written, so the bytes after a row may be written by anyone meanwhile).
+ * Row addresses are 4-byte aligned (device memory or mapped page-locked host memory); lengths are any
+ * value from 0 to symbol_size.  A row of length 0 is not touched and its address is never dereferenced
+ * (it may be 0).  Gather may read the aligned dword that holds a row's last byte (an aligned dword cannot
+ * cross a page) and never reads further.  rows[] and len[] are device-accessible arrays, so these entry
+ * points cannot check them: the kernels clamp len[x] to symbol_size, so a bad length cannot overrun
+ * the packed buffer, and trust the addresses. */
+int fecgpu_rows_gather(const uint64_t *rows, const uint32_t *len, uint64_t nrows, uint32_t symbol_size, void *dst,
+                       void *stream);
+int fecgpu_rows_scatter(const void *src, const uint64_t *rows, const uint32_t *len, uint64_t nrows,
+                        uint32_t symbol_size, void *stream);
+
+/* Device scratch of one fecgpu_rlc_encode_rows_len / fecgpu_rlc_decode_rows_len pass over a batch: the
+ * packed sources, packed repairs and packed recovered rows ([nblocks][min(k, r)]), each from a 256-B
+ * boundary, then fecgpu_rlc_decode_workspace(nblocks, k, r).  16-byte aligned.  Encode uses only the
+ * first two arrays and accepts a workspace that ends after them. */
+size_t fecgpu_rlc_rows_len_workspace(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size);
+
+/* fecgpu_rlc_encode_rows on ragged rows: blk_len[b] <= symbol_size is the length of block b (the
+ * reference's max_length) and src_len[b * k + j] <= blk_len[b] that of its source j.  Each repair row
+ * receives exactly blk_len[b] bytes: the first blk_len[b] bytes fecgpu_rlc_encode_rows gives on the same
+ * rows zero-padded to symbol_size.  Runs gather, fecgpu_rlc_encode on the packed batch, scatter: two
+ * more passes over device memory than fecgpu_rlc_encode_rows, which stays the entry point for rows of
+ * one length.  src_len[] and blk_len[] are device-accessible arrays, so this entry point cannot check
+ * them: the kernels clamp src_len to blk_len and blk_len to symbol_size instead (the host form,
+ * fecgpu_rlc_encode_rows_len_host, checks both before any launch). */
+int fecgpu_rlc_encode_rows_len(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                               const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r,
+                               uint32_t symbol_size, uint32_t fbn_base, const uint32_t *fbn, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
+/* fecgpu_rlc_decode_rows on ragged rows (reference mode).  A present source / repair is read for
+ * min(src_len / rep_len, blk_len[b]) bytes -- a received symbol longer than the block is truncated --
+ * and an absent one is not read (its address may be 0 unless it is a missing source to be written).
+ * status and recovered are exactly what fecgpu_rlc_decode_seeded gives on the rows zero-padded to
+ * symbol_size.  Every missing source whose recovered bit is set receives exactly blk_len[b] bytes at
+ * src_rows[b * k + j]; a missing source whose bit stays clear is left alone.  Nothing is ever written
+ * past blk_len[b] bytes of a row.  Runs gather (sources, repairs), the plan, fecgpu_rlc_decode_apply_packed
+ * and a scatter under recovered[].  The length tables are device-accessible arrays: the kernels clamp
+ * them as above instead of checking (fecgpu_rlc_decode_rows_len_host checks before any launch). */
+int fecgpu_rlc_decode_rows_len(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                               const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                               uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                               const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                               uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream);
 
 /* XOR encode (r == 1): rep[b][0] = XOR_j src[b][j]. */
 int fecgpu_xor_encode(const void *src, void *rep, uint64_t nblocks, uint32_t k,
@@ -258,6 +315,21 @@ int fecgpu_rlc_decode_rows_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows
                                 uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
                                 const uint32_t *rep_seed, const uint64_t *src_present, const uint64_t *rep_present,
                                 uint8_t *status, uint64_t *recovered);
+/* fecgpu_rlc_encode_rows_len / fecgpu_rlc_decode_rows_len from the host: the row tables, length tables,
+ * fbn[] / seeds, masks, status and recovered are host arrays (page-locked ones are used in place,
+ * others are copied); the rows must be device-accessible.  The batch runs in sub-batches of about
+ * chunk_bytes of payload whose packed arrays live in the context's own device buffers.  Before any
+ * launch both check blk_len[b] <= symbol_size and src_len <= blk_len[b] (decode: for the sources
+ * present) and return FECGPU_ERR_INVALID otherwise, with nothing written.  With r == 0 decode does not
+ * read the repair tables and seeds (NULL is accepted). */
+int fecgpu_rlc_encode_rows_len_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint32_t *src_len,
+                                    const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                    uint32_t r, uint32_t symbol_size, const uint32_t *fbn);
+int fecgpu_rlc_decode_rows_len_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint32_t *src_len,
+                                    const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                    uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
+                                    const uint32_t *rep_seed, const uint64_t *src_present,
+                                    const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
 /* fecgpu_rlc_window_encode_table from the host: the stream (host rows) crosses PCIe once, by one copy,
  * before the windows are coded from device memory -- a symbol serves up to k windows, so reading it in
  * place would cross the bus that many times; wrow[] is a host array; repairs go to page-locked `rep` in

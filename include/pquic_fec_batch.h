@@ -87,7 +87,12 @@ void pquic_fec_batcher_destroy(pquic_fec_batcher_t *b);
  * read source symbols and write repair symbols in it directly, and RLC recover batches read the received
  * sources and repairs in it and write each recovered source into a symbol allocated for it at submission
  * (through the bound allocator, so in the connection's arena), instead of copying rows through staging
- * rows.  Returns 0, or -1 (NULL / empty range, overlap with a registered range, registration failure). */
+ * rows.  Symbols need not be as long as the stride (max_symbol padded to 4) or as the block: a batch with
+ * ragged blocks hands every symbol over with its own length (fecgpu_rlc_encode_rows_len_host /
+ * fecgpu_rlc_decode_rows_len_host), so only the bytes that exist cross PCIe, repairs and recovered
+ * sources receive exactly the block's length, and only symbols outside every registered range are
+ * staged.  (Against an engine library without those two entry points ragged blocks are staged,
+ * zero-padded to the stride.)  Returns 0, or -1 (NULL / empty range, overlap with a registered range, registration failure). */
 int pquic_fec_batch_register_heap(pquic_fec_batcher_t *b, void *base, size_t bytes);
 /* Unregister the range registered at `base` (a connection closing).  No block whose symbols lie in it
  * may still be queued: the caller has had every done() for them.  Returns 0 or -1. */

@@ -16,8 +16,12 @@
  * Gather (pquic_fec_batch_register_heap): once the FEC plugin's memory arena is registered, a
  * generate job's stagers copy nothing for rows that lie in it -- they write the rows' device
  * addresses into page-locked tables and the kernel (fecgpu_rlc_encode_rows) reads the sources and
- * writes the repairs where the symbols are.  Rows outside a registered arena, or shorter than the
- * block's length (the reference zero-pads them), are staged as before.
+ * writes the repairs where the symbols are.  Rows outside a registered arena are staged as before.
+ * Ragged blocks -- shorter than the stride, or with symbols shorter than the block -- make their job a
+ * ragged one: it runs through fecgpu_rlc_encode_rows_len_host / fecgpu_rlc_decode_rows_len_host, which
+ * take a length per row, so every symbol in an arena is still handed over where it lies, for its own
+ * length, and only symbols outside every arena are staged (at their own length, no padding).  Against an
+ * engine without those two entry points (they are weak references) ragged blocks are staged as before.
  * Windows (pquic_fec_batch_generate_window): the sliding-window sender protects the symbols in flight
  * once per window, so consecutive windows of a connection share most of their symbols, and every window
  * is block number 0, so all windows share their coefficients.  A window job therefore stages each
@@ -42,6 +46,14 @@
 
 #include "fec_core.h"
 #include "fecgpu.h"
+
+/* The ragged-row host forms are optional: an engine without them (the CPU stand-in of the sanitizer
+ * builds) leaves these NULL and ragged blocks take the staged path. */
+#pragma weak fecgpu_rlc_encode_rows_len_host
+#pragma weak fecgpu_rlc_decode_rows_len_host
+static int rows_len_available(void) {
+    return fecgpu_rlc_encode_rows_len_host != NULL && fecgpu_rlc_decode_rows_len_host != NULL;
+}
 
 enum { OP_GENERATE = 0, OP_RECOVER = 1, OP_WINDOW = 2 /* generate, window blocks */ };
 #define GENERATES(op) ((op) != OP_RECOVER)
@@ -91,6 +103,11 @@ typedef struct job {
     uint64_t seq;                  /* flush order: completions are handed out in it */
     size_t srow_cap, rrow_cap;
     uint64_t src_dev, rep_dev;     /* device addresses of the staging rows */
+    uint32_t *slen, *rlen, *blen;  /* gather, pinned: [cap][k] source / [cap][r] repair / [cap] block lengths (NULL:
+                                    * the engine takes none, or no memory: ragged blocks are staged) */
+    size_t slen_cap, rlen_cap, blen_cap;
+    int ragged;                    /* gather: a block of the job is ragged (atomic while staging): the job runs
+                                    * through the _rows_len_host forms */
     uint8_t *copy;                 /* gather: block needs its repairs copied out of the staging rows */
     uint32_t ncopy;                /* blocks flagged in copy[] (atomic while staging) */
     uint32_t *wrow;                /* window: pinned [cap] start row of each window in the stream */
@@ -232,6 +249,9 @@ static void job_free(job_t *j) {
     free(j->order);
     fecgpu_host_free(j->srow);
     fecgpu_host_free(j->rrow);
+    fecgpu_host_free(j->slen);
+    fecgpu_host_free(j->rlen);
+    fecgpu_host_free(j->blen);
     free(j->pre);
     free(j->cpm);
     free(j->copy);
@@ -314,6 +334,23 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
     if (j->gather && (fecgpu_host_device_address(j->src, sb, &j->src_dev) != FECGPU_OK ||
                       fecgpu_host_device_address(j->rep, rb ? rb : 4, &j->rep_dev) != FECGPU_OK))
         j->gather = 0;
+    /* length tables of a gather job, where the engine takes them; without them the job stages ragged blocks */
+    if (j->gather && rows_len_available()) {
+        const size_t nr = (size_t)cap * (r ? r : 1);
+        if (j->slen_cap < (size_t)cap * k) {
+            fecgpu_host_free(j->slen);
+            j->slen_cap = (j->slen = fecgpu_host_alloc((size_t)cap * k * 4)) ? (size_t)cap * k : 0;
+        }
+        if (j->rlen_cap < nr) {
+            fecgpu_host_free(j->rlen);
+            j->rlen_cap = (j->rlen = fecgpu_host_alloc(nr * 4)) ? nr : 0;
+        }
+        if (j->blen_cap < cap) {
+            fecgpu_host_free(j->blen);
+            j->blen_cap = (j->blen = fecgpu_host_alloc((size_t)cap * 4)) ? cap : 0;
+        }
+    }
+    j->ragged = 0;
     j->ncopy = 0;
     if (op == OP_WINDOW) {  /* window tables: start rows (page-locked), the stream's symbols, the grouping */
         if (!j->wrow) j->wrow = fecgpu_host_alloc((size_t)cap * 4);
@@ -452,6 +489,11 @@ static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
     const uint32_t S = j->stride;
     if (j->op == OP_WINDOW)
         j->rc = fecgpu_rlc_window_encode_host(c, j->src, j->nrows, j->wrow, j->n, j->k, j->r, S, j->rep);
+    else if (j->gather && j->ragged && j->op == OP_RECOVER)
+        j->rc = fecgpu_rlc_decode_rows_len_host(c, j->srow, j->slen, j->rrow, j->rlen, j->blen, j->n, j->k, j->r, S,
+                                                j->seeds, j->sp, j->rp, j->st, j->rec);
+    else if (j->gather && j->ragged)
+        j->rc = fecgpu_rlc_encode_rows_len_host(c, j->srow, j->slen, j->rrow, j->blen, j->n, j->k, j->r, S, j->fbn);
     else if (j->gather && j->op == OP_RECOVER)
         j->rc = fecgpu_rlc_decode_rows_host(c, j->srow, j->rrow, j->n, j->k, j->r, S, j->seeds, j->sp, j->rp, j->st,
                                             j->rec);
@@ -467,10 +509,16 @@ static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
                                                     j->st, j->rec);
 }
 
-/* Gather: the row tables of blocks [i0, i1).  A source row is read in place when it lies in a
- * registered heap and is as long as the block (shorter ones are zero-padded, :41-55, so they are
- * staged); a repair row is written in place when its symbol is in a heap and as long as the stride
- * (the kernel writes `stride` bytes), else into the staging rows and copied out after the engine. */
+/* Gather: the row tables of blocks [i0, i1).  A whole block -- every source as long as the stride -- is
+ * coded by kernels that read and write `stride` bytes per row: a source row is read in place when it lies
+ * in a registered heap, a repair row is written in place when its symbol does, and the others go through
+ * the staging rows (repairs copied out after the engine).  Any other block is ragged and marks the job
+ * so (run_engine then takes the _rows_len form, which wants a length per row): each source that lies in a
+ * heap for its own length is read in place for that length, each repair that lies in one for the block's
+ * length receives exactly that many bytes, and only symbols outside every heap are staged, at their own
+ * length (the kernel zero-pads, :41-55).  A whole block's tables serve both forms: its lengths are the
+ * stride.  Without length tables (an engine that takes none) a ragged block keeps the rule of before:
+ * sources shorter than the block and repairs of blocks shorter than the stride are staged, zero-padded. */
 static void gather_recover_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1);
 
 static void gather_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1) {
@@ -479,13 +527,55 @@ static void gather_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_
         return;
     }
     const uint32_t S = j->stride, k = j->k, r = j->r;
+    const int lens = j->slen && j->rlen && j->blen;
     uint32_t ncopy = 0;
     uint64_t inplace = 0, staged = 0;
-    int hint = -1;
+    int hint = -1, ragged = 0;
     pthread_rwlock_rdlock(&b->heaps_mu);
     for (uint32_t i = i0; i < i1; i++) {
         const entry_t *e = &j->ent[i];
         const pquic_fec_block_t *fb = e->fb;
+        if (lens) {
+            int whole = e->maxl == S;
+            for (uint32_t x = 0; whole && x < k; x++)
+                whole = fb->source_symbols[x] && fb->source_symbols[x]->data_length == S;
+            j->blen[i] = e->maxl;
+            if (!whole) {  /* ragged: every symbol for its own length */
+                uint8_t cp = 0;
+                ragged = 1;
+                for (uint32_t x = 0; x < k; x++) {
+                    const pquic_source_symbol_t *ss = fb->source_symbols[x];
+                    const size_t o = ((size_t)i * k + x) * S;
+                    const uint16_t n = ss ? ss->data_length : 0;
+                    uint64_t d = n ? heap_dev(b, ss->data, n, &hint) : 0;
+                    if (d) {
+                        inplace++;
+                    } else {
+                        if (n) memcpy(j->src + o, ss->data, n);
+                        d = j->src_dev + o;  /* a row of no bytes is never read */
+                        staged += n != 0;
+                    }
+                    j->srow[(size_t)i * k + x] = d;
+                    j->slen[(size_t)i * k + x] = n;
+                }
+                for (uint32_t x = 0; x < r; x++) {
+                    pquic_repair_symbol_t *rs = (int)x < e->nalloc ? j->reps[(size_t)i * r + x] : NULL;
+                    uint64_t d = rs && e->maxl ? heap_dev(b, rs->data, e->maxl, &hint) : 0;
+                    if (!d) {
+                        d = j->rep_dev + ((size_t)i * r + x) * S;
+                        cp |= rs != NULL;
+                        staged += rs != NULL;
+                    } else {
+                        inplace++;
+                    }
+                    j->rrow[(size_t)i * r + x] = d;
+                }
+                j->copy[i] = cp;
+                ncopy += cp;
+                continue;
+            }
+            for (uint32_t x = 0; x < k; x++) j->slen[(size_t)i * k + x] = S;
+        }
         for (uint32_t x = 0; x < k; x++) {
             const pquic_source_symbol_t *ss = fb->source_symbols[x];
             const size_t o = ((size_t)i * k + x) * S;
@@ -518,6 +608,7 @@ static void gather_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_
         ncopy += cp;
     }
     pthread_rwlock_unlock(&b->heaps_mu);
+    if (ragged) __atomic_store_n(&j->ragged, 1, __ATOMIC_RELAXED);
     if (ncopy) __atomic_fetch_add(&j->ncopy, ncopy, __ATOMIC_RELAXED);
     __atomic_fetch_add(&b->stats.rows_in_place, inplace, __ATOMIC_RELAXED);
     __atomic_fetch_add(&b->stats.rows_staged, staged, __ATOMIC_RELAXED);
@@ -529,11 +620,17 @@ static void gather_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_
  * reach it -- and then a received source or repair row is read where it lies when it is in a registered
  * heap and at least that long (longer ones are read up to max_length, the reference's truncation, :205);
  * a missing source's row is the symbol allocated for it at submission.  Everything else is staged as
- * fec_recover_stage stages it (truncated, zero-padded), recovered bytes into the staging row. */
+ * fec_recover_stage stages it (truncated, zero-padded), recovered bytes into the staging row.
+ * With length tables (gather_blocks) a block of another length, or with a received symbol shorter than
+ * the stride, is ragged instead and marks the job so: each received symbol that lies in a heap for
+ * min(its length, max_length) bytes is read in place for that many, each symbol allocated for a missing
+ * source that lies in one for max_length bytes receives exactly that many, and only symbols outside every
+ * heap are staged, at that length without padding.  A whole block's lengths are the stride. */
 static void gather_recover_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1) {
     const uint32_t S = j->stride, k = j->k, r = j->r;
+    const int lens = j->slen && j->rlen && j->blen;
     uint64_t inplace = 0, staged = 0;
-    int hint = -1;
+    int hint = -1, ragged = 0;
     pthread_rwlock_rdlock(&b->heaps_mu);
     for (uint32_t i = i0; i < i1; i++) {
         const entry_t *e = &j->ent[i];
@@ -541,6 +638,64 @@ static void gather_recover_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0,
         const int whole = e->maxl == S;
         uint64_t *sp = j->sp + 2 * (size_t)i, *rp = j->rp + 2 * (size_t)i, *cpm = j->cpm + 2 * (size_t)i;
         sp[0] = sp[1] = rp[0] = rp[1] = cpm[0] = cpm[1] = 0;
+        if (lens) {
+            int full = whole;  /* every received symbol reaches the stride */
+            for (uint32_t x = 0; full && x < k; x++)
+                full = !fb->source_symbols[x] || fb->source_symbols[x]->data_length >= S;
+            for (uint32_t x = 0; full && x < r; x++)
+                full = !fb->repair_symbols[x] || fb->repair_symbols[x]->data_length >= S;
+            j->blen[i] = e->maxl;
+            if (!full) {  /* ragged: every symbol for its own length */
+                ragged = 1;
+                for (uint32_t x = 0; x < k; x++) {
+                    const pquic_source_symbol_t *ss = fb->source_symbols[x];
+                    const size_t o = ((size_t)i * k + x) * S;
+                    uint16_t n = 0;
+                    uint64_t d = 0;
+                    if (ss) {
+                        sp[x >> 6] |= 1ull << (x & 63);
+                        n = ss->data_length < e->maxl ? ss->data_length : e->maxl;  /* the truncation of :205 */
+                        d = n ? heap_dev(b, ss->data, n, &hint) : 0;
+                        if (d) {
+                            inplace++;
+                        } else if (n) {
+                            memcpy(j->src + o, ss->data, n);
+                            staged++;
+                        }
+                    } else {
+                        const pquic_source_symbol_t *pre = j->pre[(size_t)i * k + x];
+                        d = pre && e->maxl ? heap_dev(b, pre->data, e->maxl, &hint) : 0;
+                        inplace += d != 0;
+                        if (!d) cpm[x >> 6] |= 1ull << (x & 63);  /* recovered into the staging row */
+                    }
+                    j->srow[(size_t)i * k + x] = d ? d : j->src_dev + o;
+                    j->slen[(size_t)i * k + x] = n;
+                }
+                for (uint32_t x = 0; x < r; x++) {
+                    const pquic_repair_symbol_t *rs = fb->repair_symbols[x];
+                    const size_t o = ((size_t)i * r + x) * S;
+                    uint16_t n = 0;
+                    uint64_t d = 0;
+                    if (rs) {
+                        rp[x >> 6] |= 1ull << (x & 63);
+                        n = rs->data_length < e->maxl ? rs->data_length : e->maxl;
+                        d = n ? heap_dev(b, rs->data, n, &hint) : 0;
+                        if (d) {
+                            inplace++;
+                        } else if (n) {
+                            memcpy(j->rep + o, rs->data, n);
+                            staged++;
+                        }
+                    }
+                    j->rrow[(size_t)i * r + x] = d ? d : j->rep_dev + o;  /* absent repairs: never read */
+                    j->rlen[(size_t)i * r + x] = n;
+                    j->seeds[(size_t)i * r + x] = rs ? rs->fpid.f.source_fpid.raw : 0;
+                }
+                continue;
+            }
+            for (uint32_t x = 0; x < k; x++) j->slen[(size_t)i * k + x] = S;
+            for (uint32_t x = 0; x < r; x++) j->rlen[(size_t)i * r + x] = S;
+        }
         for (uint32_t x = 0; x < k; x++) {
             const pquic_source_symbol_t *ss = fb->source_symbols[x];
             const size_t o = ((size_t)i * k + x) * S;
@@ -586,6 +741,7 @@ static void gather_recover_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0,
         }
     }
     pthread_rwlock_unlock(&b->heaps_mu);
+    if (ragged) __atomic_store_n(&j->ragged, 1, __ATOMIC_RELAXED);
     __atomic_fetch_add(&b->stats.rows_in_place, inplace, __ATOMIC_RELAXED);
     __atomic_fetch_add(&b->stats.rows_staged, staged, __ATOMIC_RELAXED);
 }

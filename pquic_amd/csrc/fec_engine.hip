@@ -21,6 +21,8 @@
 //   k_rlc_encode_lds / k_rlc_decode_lds / k_block_svc   one block per workgroup (the synchronous hooks):
 //                  rows staged in LDS, a packed v_perm multiply (fec_device.h gf_mac) per dword.
 //   k_xor_*        XOR scheme, streaming 16-B lanes.
+//   k_rows_gather / k_rows_scatter   ragged rows (a length per row) to and from a packed batch, around
+//                  the packed encode / decode: the *_rows_len entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -3225,6 +3227,121 @@ __global__ void k_synth_fill(uint8_t *dst, uint64_t nbytes, uint64_t seed, uint6
 }
 
 // =============================================================================================
+// Ragged rows (fecgpu_rows_gather / _scatter, the *_rows_len entry points): rows of their own length,
+// given by address, to and from a packed batch of symbol_size-byte rows.  Plain copy kernels: a team of
+// FEC_ROWS_LPR lanes moves one row, 16 B per lane and step (dword-aligned 16-B accesses: a row is only
+// 4-byte aligned), so a 256-thread workgroup has 256 / FEC_ROWS_LPR rows in flight.
+// =============================================================================================
+// Lanes per row, measured on 2^20 rows of 1200 B (profiles/ragged_rows.log; A/B builds define another):
+// 32 lanes, 8 rows per workgroup, is kept -- gather from page-locked host rows 51 GiB/s against 42 with 16
+// lanes and 36 with 8, device rows 2.4 TiB/s against 2.1 and 1.5; 64 lanes read host rows as fast (52) but
+// lose a quarter on ragged device rows, where most of a wave's second step has no bytes left to move.
+#ifndef FEC_ROWS_LPR
+#define FEC_ROWS_LPR 32
+#endif
+typedef uint32_t rows_u32x4 __attribute__((ext_vector_type(4)));
+typedef rows_u32x4 rows_u32x4_a4 __attribute__((aligned(4)));
+// a row address comes out of a table as an integer: cast to the global address space, or the accesses
+// compile to flat instructions
+#define ROWS_GLOBAL __attribute__((address_space(1)))
+
+// bit j of the two-word mask of block b
+__device__ __forceinline__ bool rows_bit(const uint64_t *m, uint64_t b, int j) {
+  return (m[2 * b + (j >> 6)] >> (j & 63)) & 1;
+}
+
+// Row x of the table -> dst + x * L: n bytes, then zeros up to L.  n = len[x] clamped to L, to
+// blk_len[x / per] (if given), and 0 where the row's bit of present[] (if given) is clear; a row of 0
+// bytes is never dereferenced.  The last 1-3 bytes come from the aligned dword that holds them, masked.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_rows_gather(const uint64_t *__restrict__ rows, const uint32_t *__restrict__ len,
+                                                     uint64_t nrows, int L, uint8_t *__restrict__ dst,
+                                                     const uint32_t *__restrict__ blk_len,
+                                                     const uint64_t *__restrict__ present, int per) {
+  constexpr int RPW = 256 / LPR;
+  const int sub = threadIdx.x % LPR, Lw = L >> 2;
+  for (uint64_t x = (uint64_t)blockIdx.x * RPW + threadIdx.x / LPR; x < nrows; x += (uint64_t)gridDim.x * RPW) {
+    const uint64_t b = x / (uint32_t)per;
+    uint32_t n = len[x];
+    if (n > (uint32_t)L) n = (uint32_t)L;
+    if (blk_len && n > blk_len[b]) n = blk_len[b];
+    if (present && !rows_bit(present, b, (int)(x - b * (uint32_t)per))) n = 0;
+    const int nd = (int)(n >> 2), t = (int)(n & 3);
+    const ROWS_GLOBAL uint32_t *a = n ? (const ROWS_GLOBAL uint32_t *)rows[x] : nullptr;
+    uint32_t *d = reinterpret_cast<uint32_t *>(dst + x * (uint64_t)L);
+    for (int w = sub * 4; w < Lw; w += LPR * 4) {
+      rows_u32x4 v = {0u, 0u, 0u, 0u};
+      if (w + 4 <= nd) {
+        v = *(const ROWS_GLOBAL rows_u32x4_a4 *)(a + w);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          if (w + i < nd) v[i] = a[w + i];
+          else if (w + i == nd && t) v[i] = a[nd] & ((1u << (8 * t)) - 1u);
+        }
+      }
+      if (w + 4 <= Lw) {
+        *reinterpret_cast<rows_u32x4_a4 *>(d + w) = v;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          if (w + i < Lw) d[w + i] = v[i];
+      }
+    }
+  }
+}
+
+// n bytes of a packed row -> the address of row x of the table, and not one byte more: 16-B stores, then
+// dword stores, then byte stores for the last 1-3 bytes (no dword is read-modify-written: its other
+// bytes are not ours).  n = len[x] (if given) clamped to blk_len[x / per] (if given) and to L.  Rows of 0
+// bytes and rows whose bit of mask[] (if given) is clear are not touched.  The packed row is row x of
+// src, or with present[] given (the recover side) row (x / per) * em + u, u the number of clear bits of
+// present[] below the row's own: fecgpu_rlc_decode_apply_packed's layout.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_rows_scatter(const uint8_t *__restrict__ src, const uint64_t *__restrict__ rows,
+                                                      const uint32_t *__restrict__ len, uint64_t nrows, int L,
+                                                      const uint32_t *__restrict__ blk_len,
+                                                      const uint64_t *__restrict__ mask,
+                                                      const uint64_t *__restrict__ present, int per, int em) {
+  constexpr int RPW = 256 / LPR;
+  const int sub = threadIdx.x % LPR;
+  for (uint64_t x = (uint64_t)blockIdx.x * RPW + threadIdx.x / LPR; x < nrows; x += (uint64_t)gridDim.x * RPW) {
+    const uint64_t b = x / (uint32_t)per;
+    const int j = (int)(x - b * (uint32_t)per);
+    uint32_t n = len ? len[x] : blk_len[b];
+    if (len && blk_len && n > blk_len[b]) n = blk_len[b];
+    if (n > (uint32_t)L) n = (uint32_t)L;
+    if (mask && !rows_bit(mask, b, j)) n = 0;
+    uint64_t srow = x;
+    if (present) {
+      const uint64_t p0 = ~present[2 * b], p1 = ~present[2 * b + 1];
+      const int u = j < 64 ? __popcll(p0 & ((1ull << j) - 1ull))
+                           : __popcll(p0) + __popcll(p1 & ((1ull << (j - 64)) - 1ull));
+      if (u >= em) n = 0;
+      srow = b * (uint32_t)em + (uint32_t)u;
+    }
+    if (n == 0) continue;
+    const int nd = (int)(n >> 2), t = (int)(n & 3);
+    const uint32_t *s = reinterpret_cast<const uint32_t *>(src + srow * (uint64_t)L);
+    ROWS_GLOBAL uint32_t *a = (ROWS_GLOBAL uint32_t *)rows[x];
+    for (int w = sub * 4; w < nd; w += LPR * 4) {
+      if (w + 4 <= nd) {
+        *(ROWS_GLOBAL rows_u32x4_a4 *)(a + w) = *reinterpret_cast<const rows_u32x4_a4 *>(s + w);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+          if (w + i < nd) a[w + i] = s[w + i];
+      }
+    }
+    if (t && sub == (nd >> 2) % LPR) {  // the team's lane that would own dword nd
+      const uint32_t v = s[nd];         // inside the packed row: nd < L / 4 when t != 0
+      ROWS_GLOBAL uint8_t *tail = (ROWS_GLOBAL uint8_t *)(a + nd);
+      for (int i = 0; i < t; i++) tail[i] = (uint8_t)(v >> (8 * i));
+    }
+  }
+}
+
+// =============================================================================================
 // Launch configuration
 // =============================================================================================
 static int pick_rt(uint32_t r) { return r >= 16 ? 16 : r >= 8 ? 8 : r >= 4 ? 4 : r >= 2 ? 2 : 1; }
@@ -3679,6 +3796,137 @@ int fecgpu_rlc_decode_rows(const uint64_t *src_rows, const uint64_t *rep_rows, u
   }
   HIPCHK(hipGetLastError());
   return fused ? FECGPU_OK : launch_finalize(nblocks, k, r, status, recovered, ws, s);
+}
+
+// ---- ragged rows ----
+static uint32_t rows_grid(uint64_t nrows) {
+  constexpr uint64_t rpw = 256 / FEC_ROWS_LPR;
+  const uint64_t wgs = (nrows + rpw - 1) / rpw;
+  return (uint32_t)(wgs < 65536 ? wgs : 65536);  // grid-stride beyond: 8 waves per SIMD of every CU, many times over
+}
+
+static int launch_gather(const uint64_t *rows, const uint32_t *len, uint64_t nrows, uint32_t L, void *dst,
+                         const uint32_t *blk_len, const uint64_t *present, uint32_t per, hipStream_t s) {
+  if (nrows == 0) return FECGPU_OK;
+  hipLaunchKernelGGL(k_rows_gather<FEC_ROWS_LPR>, dim3(rows_grid(nrows)), dim3(256), 0, s, rows, len, nrows, (int)L,
+                     (uint8_t *)dst, blk_len, present, (int)per);
+  HIPCHK(hipGetLastError());
+  return FECGPU_OK;
+}
+
+static int launch_scatter(const void *src, const uint64_t *rows, const uint32_t *len, uint64_t nrows, uint32_t L,
+                          const uint32_t *blk_len, const uint64_t *mask, const uint64_t *present, uint32_t per,
+                          uint32_t em, hipStream_t s) {
+  if (nrows == 0) return FECGPU_OK;
+  hipLaunchKernelGGL(k_rows_scatter<FEC_ROWS_LPR>, dim3(rows_grid(nrows)), dim3(256), 0, s, (const uint8_t *)src, rows,
+                     len, nrows, (int)L, blk_len, mask, present, (int)per, (int)em);
+  HIPCHK(hipGetLastError());
+  return FECGPU_OK;
+}
+
+static int rows_args(const void *rows, const void *len, const void *packed, uint64_t nrows, uint32_t L) {
+  if (int rc = check_common(rows, packed, nrows, 1, 0, L)) return rc;
+  if (nrows && !len) return set_err(FECGPU_ERR_INVALID, "%s", "NULL length table");
+  return FECGPU_OK;
+}
+
+int fecgpu_rows_gather(const uint64_t *rows, const uint32_t *len, uint64_t nrows, uint32_t symbol_size, void *dst,
+                       void *stream) {
+  if (int rc = rows_args(rows, len, dst, nrows, symbol_size)) return rc;
+  return launch_gather(rows, len, nrows, symbol_size, dst, nullptr, nullptr, 1, (hipStream_t)stream);
+}
+
+int fecgpu_rows_scatter(const void *src, const uint64_t *rows, const uint32_t *len, uint64_t nrows,
+                        uint32_t symbol_size, void *stream) {
+  if (int rc = rows_args(rows, len, src, nrows, symbol_size)) return rc;
+  return launch_scatter(src, rows, len, nrows, symbol_size, nullptr, nullptr, nullptr, 1, 0, (hipStream_t)stream);
+}
+
+// the packed arrays of one pass, each from a 256-B boundary, then the decode workspace
+static inline size_t rows_len_pad(size_t n) { return (n + 255) & ~(size_t)255; }
+struct RowsLenWs { size_t rep, rec, dec, total; };
+static RowsLenWs rows_len_ws(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L) {
+  RowsLenWs w;
+  const uint32_t em = k < r ? k : r;
+  w.rep = rows_len_pad((size_t)nblocks * k * L);
+  w.rec = w.rep + rows_len_pad((size_t)nblocks * r * L);
+  w.dec = w.rec + rows_len_pad((size_t)nblocks * em * L);
+  w.total = w.dec + fecgpu_rlc_decode_workspace(nblocks, k, r);
+  return w;
+}
+
+size_t fecgpu_rlc_rows_len_workspace(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size) {
+  return rows_len_ws(nblocks, k, r, symbol_size).total;
+}
+
+// gather -> packed encode -> scatter, with the packed arrays given (the host forms pass a slot's buffers)
+extern "C" __attribute__((visibility("hidden"))) int fecgpu_rlc_encode_rows_len_internal(
+    const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows, const uint32_t *blk_len,
+    uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, uint32_t fbn_base, const uint32_t *fbn, void *psrc,
+    void *prep, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = launch_gather(src_rows, src_len, nblocks * k, L, psrc, blk_len, nullptr, k, s)) return rc;
+  if (int rc = fecgpu_rlc_encode(psrc, prep, nblocks, k, r, L, fbn_base, fbn, s)) return rc;
+  return launch_scatter(prep, rep_rows, nullptr, nblocks * r, L, blk_len, nullptr, nullptr, r, 0, s);
+}
+
+int fecgpu_rlc_encode_rows_len(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                               const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r,
+                               uint32_t symbol_size, uint32_t fbn_base, const uint32_t *fbn, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+  int rc = check_common(src_rows, rep_rows, nblocks, k, r, symbol_size);
+  if (rc || nblocks == 0 || r == 0) return rc;
+  if (!src_len || !blk_len || !workspace) return set_err(FECGPU_ERR_INVALID, "%s", "NULL length table / workspace");
+  if ((uintptr_t)workspace % 16) return set_err(FECGPU_ERR_INVALID, "%s", "workspace must be 16-byte aligned");
+  const RowsLenWs W = rows_len_ws(nblocks, k, r, symbol_size);
+  if (workspace_bytes < W.rec) return set_err(FECGPU_ERR_NOMEM, "%s", "rows_len workspace too small");
+  uint8_t *ws = (uint8_t *)workspace;
+  return fecgpu_rlc_encode_rows_len_internal(src_rows, src_len, rep_rows, blk_len, nblocks, k, r, symbol_size,
+                                             fbn_base, fbn, ws, ws + W.rep, stream);
+}
+
+// gather sources and repairs -> plan -> packed apply -> scatter of the recovered rows, with the packed
+// arrays and the plan workspace given.  The scatter runs under recovered[]: exactly the missing sources
+// the data pass reports get their blk_len bytes.
+extern "C" __attribute__((visibility("hidden"))) int fecgpu_rlc_decode_rows_len_internal(
+    const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows, const uint32_t *rep_len,
+    const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *rep_seed,
+    const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered, void *psrc, void *prep, void *prec,
+    void *ws, size_t wsb, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t em = k < r ? k : r;
+  int rc = decode_plan_impl(nblocks, k, r, 0, nullptr, rep_seed, sp, rp, ws, wsb, s);
+  if (rc) return rc;
+  if ((rc = launch_gather(src_rows, src_len, nblocks * k, L, psrc, blk_len, sp, k, s))) return rc;
+  if ((rc = launch_gather(rep_rows, rep_len, nblocks * r, L, prep, blk_len, rp, r, s))) return rc;
+  if ((rc = decode_apply_impl(psrc, prep, prec, nblocks, k, r, L, status, recovered, ws, wsb, s, em ? (int)em : 1)))
+    return rc;
+  return launch_scatter(prec, src_rows, nullptr, em ? nblocks * k : 0, L, blk_len, recovered, sp, k, em, s);
+}
+
+int fecgpu_rlc_decode_rows_len(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                               const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                               uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                               const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                               uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream) {
+  int rc = check_common(src_rows, rep_rows, nblocks, k, r, symbol_size);
+  if (rc || nblocks == 0) return rc;
+  if (!src_len || !blk_len || (r && !rep_len)) return set_err(FECGPU_ERR_INVALID, "%s", "NULL length table");
+  if (!src_present || !rep_present || !status || !recovered || !workspace)
+    return set_err(FECGPU_ERR_INVALID, "%s", "NULL mask/status/workspace");
+  if (r && !rep_seed) return set_err(FECGPU_ERR_INVALID, "%s", "NULL rep_seed");
+  if ((uintptr_t)workspace % 16) return set_err(FECGPU_ERR_INVALID, "%s", "workspace must be 16-byte aligned");
+  const RowsLenWs W = rows_len_ws(nblocks, k, r, symbol_size);
+  if (workspace_bytes < W.total) return set_err(FECGPU_ERR_NOMEM, "%s", "rows_len workspace too small");
+  uint8_t *ws = (uint8_t *)workspace;
+  return fecgpu_rlc_decode_rows_len_internal(src_rows, src_len, rep_rows, rep_len, blk_len, nblocks, k, r,
+                                             symbol_size, rep_seed, src_present, rep_present, status, recovered, ws,
+                                             ws + W.rep, ws + W.rec, ws + W.dec, W.total - W.dec, stream);
+}
+
+// host_path.hip's argument errors (library-internal): the message fecgpu_last_error() returns
+extern "C" __attribute__((visibility("hidden"))) int fecgpu_set_error_internal(int code, const char *what) {
+  return set_err(code, "%s", what);
 }
 
 extern "C++" {

@@ -610,6 +610,187 @@ int fecgpu_rlc_decode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, 
   return finish(c, rc);
 }
 
+// ---- ragged rows (fecgpu_rlc_encode_rows_len_host / fecgpu_rlc_decode_rows_len_host) ----
+// fec_engine.hip (library-internal): the device forms with the packed arrays given one by one, so a
+// sub-batch packs into its slot's d_src / d_rep and plans in its d_ws
+int fecgpu_rlc_encode_rows_len_internal(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                        const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L,
+                                        uint32_t fbn_base, const uint32_t *fbn, void *psrc, void *prep, void *stream);
+int fecgpu_rlc_decode_rows_len_internal(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                        const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                        uint32_t r, uint32_t L, const uint32_t *rep_seed, const uint64_t *sp,
+                                        const uint64_t *rp, uint8_t *status, uint64_t *recovered, void *psrc,
+                                        void *prep, void *prec, void *ws, size_t wsb, void *stream);
+int fecgpu_set_error_internal(int code, const char *what);
+
+static int rows_len_invalid(const char *what) { return fecgpu_set_error_internal(FECGPU_ERR_INVALID, what); }
+
+// check_common's shape rules (the tables are checked by the callers)
+static int rows_len_shape(uint32_t k, uint32_t r, uint32_t L) {
+  if (k < 1 || k > FECGPU_MAX_K) return rows_len_invalid("k out of range [1,128]");
+  if (r > FECGPU_MAX_R) return rows_len_invalid("r out of range [0,128]");
+  if (L == 0 || (L & 3) || L > 65532) return rows_len_invalid("symbol_size must be a positive multiple of 4 (<= 65532)");
+  return FECGPU_OK;
+}
+
+// src_len <= blk_len <= symbol_size, for every source (sp == nullptr) or the sources present
+static int rows_len_check(const uint32_t *src_len, const uint32_t *blk_len, const uint64_t *sp, uint64_t nblocks,
+                          uint32_t k, uint32_t L) {
+  for (uint64_t b = 0; b < nblocks; b++) {
+    if (blk_len[b] > L) return rows_len_invalid("blk_len above symbol_size");
+    for (uint32_t j = 0; j < k; j++) {
+      if (sp && !((sp[2 * b + (j >> 6)] >> (j & 63)) & 1)) continue;
+      if (src_len[b * k + j] > blk_len[b]) return rows_len_invalid("src_len above blk_len");
+    }
+  }
+  return FECGPU_OK;
+}
+
+static inline size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+int fecgpu_rlc_encode_rows_len_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                    const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                    uint32_t r, uint32_t L, const uint32_t *fbn) {
+  if (!src_rows || !src_len || !rep_rows || !blk_len) return rows_len_invalid("NULL row / length table");
+  if (int rc = rows_len_shape(k, r, L)) return rc;
+  if (int rc = rows_len_check(src_len, blk_len, nullptr, nblocks, k, L)) return rc;
+  if (!c) return rows_len_invalid("NULL host context");
+  if (!nblocks || !r) return FECGPU_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HCHK(hipSetDevice(c->device));
+  Slot &s = c->slot[0];
+  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
+  const uint64_t *dr = ds ? (const uint64_t *)mapped_host(rep_rows, nblocks * r * 8) : nullptr;
+  const uint32_t *dsl = dr ? (const uint32_t *)mapped_host(src_len, nblocks * k * 4) : nullptr;
+  const uint32_t *dbl = dsl ? (const uint32_t *)mapped_host(blk_len, nblocks * 4) : nullptr;
+  const uint32_t *df = dbl && fbn ? (const uint32_t *)mapped_host(fbn, nblocks * 4) : nullptr;
+  const bool in_place = dbl && (!fbn || df);
+  int rc = FECGPU_OK;
+  do {
+    if (!in_place) {  // pageable tables: one device copy, and the whole batch on this slot's stream
+      const size_t o_rep = nblocks * k * 8, o_sl = o_rep + nblocks * r * 8, o_bl = o_sl + nblocks * k * 4,
+                   o_fbn = o_bl + nblocks * 4;
+      LCHK(grow(&s.d_aux, &s.cap_aux, o_fbn + (fbn ? nblocks * 4 : 0)));
+      uint8_t *a = (uint8_t *)s.d_aux;
+      LCHK(hipMemcpyAsync(a, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync(a + o_rep, rep_rows, nblocks * r * 8, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync(a + o_sl, src_len, nblocks * k * 4, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync(a + o_bl, blk_len, nblocks * 4, hipMemcpyHostToDevice, s.st));
+      if (fbn) LCHK(hipMemcpyAsync(a + o_fbn, fbn, nblocks * 4, hipMemcpyHostToDevice, s.st));
+      ds = (const uint64_t *)a;
+      dr = (const uint64_t *)(a + o_rep);
+      dsl = (const uint32_t *)(a + o_sl);
+      dbl = (const uint32_t *)(a + o_bl);
+      df = fbn ? (const uint32_t *)(a + o_fbn) : nullptr;
+    }
+    Pacer pc(c, nblocks, (size_t)(k + r) * L);  // hooks in use: slices that yield to them
+    if (!in_place) pc.slice = 0;
+    const uint64_t step = pc.slice ? pc.slice : sub_batch(c, nblocks, (size_t)(k + r) * L);
+    int si = 0;
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += step) {
+      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
+      LCHK(pc.before());
+      Slot &w = c->slot[pc.slice ? pc.n % pc.streams : si];  // the packed rows of a sub-batch: its slot's buffers
+      LCHK(grow(&w.d_src, &w.cap_src, step * k * L));
+      LCHK(grow(&w.d_rep, &w.cap_rep, step * r * L));
+      // without fbn[] block b is block number b (fecgpu.h:21): sub-batch b0 starts at b0, not 0
+      if ((rc = fecgpu_rlc_encode_rows_len_internal(ds + b0 * k, dsl + b0 * k, dr + b0 * r, dbl + b0, m, k, r, L,
+                                                    df ? 0u : (uint32_t)(b0 & 0xffffffu), df ? df + b0 : nullptr,
+                                                    w.d_src, w.d_rep, w.st)))
+        break;
+      LCHK(pc.after());
+      if (in_place) si = (si + 1) % c->ns;
+    }
+  } while (0);
+  return finish(c, rc);
+}
+
+int fecgpu_rlc_decode_rows_len_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                    const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                    uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
+                                    const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+  if (!src_rows || !src_len || !blk_len || (r && (!rep_rows || !rep_len || !seeds)))
+    return rows_len_invalid("NULL row / length table");
+  if (!sp || !rp || !status || !recovered) return rows_len_invalid("NULL mask/status");
+  if (int rc = rows_len_shape(k, r, L)) return rc;
+  if (int rc = rows_len_check(src_len, blk_len, sp, nblocks, k, L)) return rc;
+  if (!c) return rows_len_invalid("NULL host context");
+  if (!nblocks) return FECGPU_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HCHK(hipSetDevice(c->device));
+  Slot &s = c->slot[0];
+  const uint32_t nseed = r ? r : 1, em = k < r ? k : r;
+  // every array page-locked (the batching adapter's job tables): the kernels use them in place.  With
+  // r == 0 the repair tables and seeds have no entries and are never read: the source tables stand in
+  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
+  const uint32_t *dsl = ds ? (const uint32_t *)mapped_host(src_len, nblocks * k * 4) : nullptr;
+  const uint32_t *dbl = dsl ? (const uint32_t *)mapped_host(blk_len, nblocks * 4) : nullptr;
+  const uint64_t *dr = !dbl ? nullptr : r ? (const uint64_t *)mapped_host(rep_rows, nblocks * r * 8) : ds;
+  const uint32_t *drl = !dr ? nullptr : r ? (const uint32_t *)mapped_host(rep_len, nblocks * r * 4) : dsl;
+  const uint32_t *dseed = !drl ? nullptr : r ? (const uint32_t *)mapped_host(seeds, nblocks * r * 4) : dsl;
+  const uint64_t *dsp = dseed ? (const uint64_t *)mapped_host(sp, nblocks * 16) : nullptr;
+  const uint64_t *drp = dsp ? (const uint64_t *)mapped_host(rp, nblocks * 16) : nullptr;
+  uint8_t *dst = drp ? mapped_host(status, nblocks) : nullptr;
+  uint64_t *drec = dst ? (uint64_t *)mapped_host(recovered, nblocks * 16) : nullptr;
+  const bool in_place = drec != nullptr;
+  int rc = FECGPU_OK;
+  do {
+    if (!in_place) {  // pageable: one device copy of the tables and masks, the whole batch on this slot's stream
+      const size_t o_rep = nblocks * k * 8, o_m = o_rep + nblocks * nseed * 8, o_sl = o_m + nblocks * 48,
+                   o_rl = o_sl + nblocks * k * 4, o_bl = o_rl + nblocks * nseed * 4, o_seed = o_bl + nblocks * 4,
+                   o_st = o_seed + nblocks * nseed * 4;
+      LCHK(grow(&s.d_aux, &s.cap_aux, o_st + nblocks));
+      uint8_t *a = (uint8_t *)s.d_aux;
+      ds = (const uint64_t *)a;
+      dr = (const uint64_t *)(a + o_rep);
+      uint64_t *mk = (uint64_t *)(a + o_m);
+      dsp = mk;
+      drp = mk + 2 * nblocks;
+      drec = mk + 4 * nblocks;
+      dsl = (const uint32_t *)(a + o_sl);
+      drl = (const uint32_t *)(a + o_rl);
+      dbl = (const uint32_t *)(a + o_bl);
+      dseed = (const uint32_t *)(a + o_seed);
+      dst = a + o_st;
+      LCHK(hipMemcpyAsync((void *)ds, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync((void *)dsl, src_len, nblocks * k * 4, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync((void *)dbl, blk_len, nblocks * 4, hipMemcpyHostToDevice, s.st));
+      if (r) {
+        LCHK(hipMemcpyAsync((void *)dr, rep_rows, nblocks * r * 8, hipMemcpyHostToDevice, s.st));
+        LCHK(hipMemcpyAsync((void *)drl, rep_len, nblocks * r * 4, hipMemcpyHostToDevice, s.st));
+        LCHK(hipMemcpyAsync((void *)dseed, seeds, nblocks * r * 4, hipMemcpyHostToDevice, s.st));
+      }
+      LCHK(hipMemcpyAsync((void *)dsp, sp, nblocks * 16, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync((void *)drp, rp, nblocks * 16, hipMemcpyHostToDevice, s.st));
+    }
+    Pacer pc(c, nblocks, (size_t)(k + r) * L);  // hooks in use: slices that yield to them
+    if (!in_place) pc.slice = 0;
+    const uint64_t step = pc.slice ? pc.slice : sub_batch(c, nblocks, (size_t)(k + r) * L);
+    const size_t o_rec = pad256(step * r * L);
+    int si = 0;
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += step) {
+      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
+      LCHK(pc.before());
+      Slot &w = c->slot[pc.slice ? pc.n % pc.streams : si];  // packed sources in d_src, repairs and recovered rows in d_rep
+      LCHK(grow(&w.d_src, &w.cap_src, step * k * L));
+      LCHK(grow(&w.d_rep, &w.cap_rep, o_rec + pad256(step * em * L) + 256));
+      LCHK(grow(&w.d_ws, &w.cap_ws, fecgpu_rlc_decode_workspace(step, k, r)));
+      if ((rc = fecgpu_rlc_decode_rows_len_internal(ds + b0 * k, dsl + b0 * k, dr + b0 * nseed, drl + b0 * nseed,
+                                                    dbl + b0, m, k, r, L, dseed + b0 * nseed, dsp + 2 * b0,
+                                                    drp + 2 * b0, dst + b0, drec + 2 * b0, w.d_src, w.d_rep,
+                                                    (uint8_t *)w.d_rep + o_rec, w.d_ws, w.cap_ws, w.st)))
+        break;
+      LCHK(pc.after());
+      if (in_place) si = (si + 1) % c->ns;
+    }
+    if (rc == FECGPU_OK && !in_place) {
+      LCHK(hipMemcpyAsync(status, dst, nblocks, hipMemcpyDeviceToHost, s.st));
+      LCHK(hipMemcpyAsync(recovered, drec, nblocks * 16, hipMemcpyDeviceToHost, s.st));
+    }
+  } while (0);
+  return finish(c, rc);
+}
+
 int fecgpu_xor_decode_host(fecgpu_host_ctx_t *c, void *src, const void *rep, uint64_t nblocks, uint32_t k,
                            uint32_t L, const uint64_t *sp, const uint64_t *rp, uint8_t *status,
                            uint64_t *recovered) {

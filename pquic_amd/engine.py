@@ -99,6 +99,16 @@ def load_library(path: str = LIB_PATH, private: bool = False):
         L.fecgpu_rlc_decode_plan_full.argtypes = [u64, u32, u32, u32, v, v, v, v, v, sz, v]
         L.fecgpu_rlc_decode_full.argtypes = [v, v, u64, u32, u32, u32, u32, v, v, v, v, v, v, v, sz, v]
         L.fecgpu_rlc_decode_host_full.argtypes = [v, v, v, u64, u32, u32, u32, u32, v, v, v, v, v, v]
+    if hasattr(L, "fecgpu_rlc_encode_rows_len"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
+        L.fecgpu_rows_gather.argtypes = [v, v, u64, u32, v, v]
+        L.fecgpu_rows_scatter.argtypes = [v, v, v, u64, u32, v]
+        L.fecgpu_rlc_rows_len_workspace.argtypes = [u64, u32, u32, u32]
+        L.fecgpu_rlc_rows_len_workspace.restype = sz
+        L.fecgpu_rlc_encode_rows.argtypes = [v, v, u64, u32, u32, u32, u32, v, v]
+        L.fecgpu_rlc_encode_rows_len.argtypes = [v, v, v, v, u64, u32, u32, u32, u32, v, v, sz, v]
+        L.fecgpu_rlc_decode_rows_len.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v, v, sz, v]
+        L.fecgpu_rlc_encode_rows_len_host.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v]
+        L.fecgpu_rlc_decode_rows_len_host.argtypes = [v, v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v]
     if not private:
         _lib = L
     return L
@@ -332,6 +342,54 @@ class Engine:
                                                   self._stream(stream)), "fecgpu_xor_decode_to")
         return status, recovered
 
+    # ------------------------------------------------------------------ ragged rows
+    def rows_gather(self, rows, lens, nrows: int, L: int, dst, stream=None):
+        """fecgpu_rows_gather: row x (address rows[x], u64; lens[x] bytes, u32) -> dst[x], zero-padded to L."""
+        self._check(self.lib.fecgpu_rows_gather(_addr(rows), _addr(lens), nrows, L, _addr(dst),
+                                                self._stream(stream)), "fecgpu_rows_gather")
+        return dst
+
+    def rows_scatter(self, src, rows, lens, nrows: int, L: int, stream=None):
+        """fecgpu_rows_scatter: lens[x] bytes of packed row src[x] -> address rows[x], not a byte more."""
+        self._check(self.lib.fecgpu_rows_scatter(_addr(src), _addr(rows), _addr(lens), nrows, L,
+                                                 self._stream(stream)), "fecgpu_rows_scatter")
+
+    def rows_len_workspace_bytes(self, nblocks: int, k: int, r: int, L: int) -> int:
+        return int(self.lib.fecgpu_rlc_rows_len_workspace(nblocks, k, r, L))
+
+    def alloc_rows_len_workspace(self, nblocks: int, k: int, r: int, L: int):
+        n = self.rows_len_workspace_bytes(nblocks, k, r, L)
+        return self.torch.empty(max(n, 16), dtype=self.torch.uint8, device=f"cuda:{self.device}")
+
+    def rlc_encode_rows(self, src_rows, rep_rows, nblocks: int, k: int, r: int, L: int, fbn_base: int = 0,
+                        fbn=None, stream=None):
+        """fecgpu_rlc_encode_rows: every row of L bytes given by its device address (u64 tables)."""
+        self._check(self.lib.fecgpu_rlc_encode_rows(_addr(src_rows), _addr(rep_rows), nblocks, k, r, L, fbn_base,
+                                                    _addr(fbn), self._stream(stream)), "fecgpu_rlc_encode_rows")
+
+    def rlc_encode_rows_len(self, src_rows, src_len, rep_rows, blk_len, nblocks: int, k: int, r: int, L: int,
+                            fbn_base: int = 0, fbn=None, workspace=None, stream=None):
+        """fecgpu_rlc_encode_rows_len: ragged rows -- src_len[b*k+j] <= blk_len[b] <= L (u32 device arrays);
+        every repair row receives exactly blk_len[b] bytes."""
+        if workspace is None:
+            workspace = self.alloc_rows_len_workspace(nblocks, k, r, L)
+        self._check(self.lib.fecgpu_rlc_encode_rows_len(
+            _addr(src_rows), _addr(src_len), _addr(rep_rows), _addr(blk_len), nblocks, k, r, L, fbn_base,
+            _addr(fbn), _addr(workspace), workspace.numel(), self._stream(stream)), "fecgpu_rlc_encode_rows_len")
+
+    def rlc_decode_rows_len(self, src_rows, src_len, rep_rows, rep_len, blk_len, rep_seed, src_present,
+                            rep_present, status, recovered, nblocks: int, k: int, r: int, L: int,
+                            workspace=None, stream=None):
+        """fecgpu_rlc_decode_rows_len: ragged rows, per-repair seeds; every missing source whose recovered
+        bit is set receives exactly blk_len[b] bytes at src_rows[b*k+j]."""
+        if workspace is None:
+            workspace = self.alloc_rows_len_workspace(nblocks, k, r, L)
+        self._check(self.lib.fecgpu_rlc_decode_rows_len(
+            _addr(src_rows), _addr(src_len), _addr(rep_rows), _addr(rep_len), _addr(blk_len), nblocks, k, r, L,
+            _addr(rep_seed), _addr(src_present), _addr(rep_present), _addr(status), _addr(recovered),
+            _addr(workspace), workspace.numel(), self._stream(stream)), "fecgpu_rlc_decode_rows_len")
+        return status, recovered
+
     def synth_fill(self, dst, nbytes: int, seed: int, offset: int = 0, stream=None):
         self._check(self.lib.fecgpu_synth_fill(_addr(dst), nbytes, seed, offset, self._stream(stream)),
                     "fecgpu_synth_fill")
@@ -382,3 +440,18 @@ class HostPath:
         self._chk(self.lib.fecgpu_rlc_decode_host_full(self.ctx, _addr(src), _addr(rep), nblocks, k, r, L, fbn_base,
                                                        _addr(fbn), _addr(seeds), _addr(sp), _addr(rp),
                                                        _addr(status), _addr(rec)), "fecgpu_rlc_decode_host_full")
+
+    def rlc_encode_rows_len(self, src_rows, src_len, rep_rows, blk_len, nblocks, k, r, L, fbn=None):
+        """fecgpu_rlc_encode_rows_len_host: host tables and lengths; the rows must be device-accessible."""
+        self._chk(self.lib.fecgpu_rlc_encode_rows_len_host(self.ctx, _addr(src_rows), _addr(src_len),
+                                                           _addr(rep_rows), _addr(blk_len), nblocks, k, r, L,
+                                                           _addr(fbn)), "fecgpu_rlc_encode_rows_len_host")
+
+    def rlc_decode_rows_len(self, src_rows, src_len, rep_rows, rep_len, blk_len, seeds, sp, rp, status, rec,
+                            nblocks, k, r, L):
+        """fecgpu_rlc_decode_rows_len_host: host tables, lengths, seeds, masks, status and recovered."""
+        self._chk(self.lib.fecgpu_rlc_decode_rows_len_host(self.ctx, _addr(src_rows), _addr(src_len),
+                                                           _addr(rep_rows), _addr(rep_len), _addr(blk_len),
+                                                           nblocks, k, r, L, _addr(seeds), _addr(sp), _addr(rp),
+                                                           _addr(status), _addr(rec)),
+                  "fecgpu_rlc_decode_rows_len_host")

@@ -264,6 +264,32 @@ void bl_set_options(unsigned poll_blocks, int hugepages, int detail, long pool_b
     if (pool_blocks > 0) g_pool_blocks = pool_blocks;
 }
 
+/* Ragged mode of the next bl_run / bl_run_recover / bl_run_senders (0: off, the default): the batcher is
+ * opened with max_symbol `max_symbol` (>= the runs' L), L becomes the block length, and every packet's
+ * length is drawn from a fixed distribution seeded by `seed` -- half the packets full (L bytes), a
+ * quarter uniform in [L/2, L], a quarter uniform in [40, L/2] (short ones: acknowledgement-sized up),
+ * one packet of every block full so the block's length is L.  A packet's length depends only on its
+ * place in the payload pool, so every run with one seed sees the same lengths.  out[0] then counts the
+ * bytes the packets hold. */
+static int g_ragged_max;
+static uint64_t g_ragged_seed;
+void bl_set_ragged(int max_symbol, unsigned seed) {
+    g_ragged_max = max_symbol > 0 ? max_symbol : 0;
+    g_ragged_seed = seed;
+}
+
+/* length of packet j of pool block q of connection c (ragged mode) */
+static uint16_t ragged_len(int c, long q, int j, int k, int L) {
+    if (j == (int)(q % k)) return (uint16_t)L;
+    uint64_t x = g_ragged_seed * 0x9E3779B97F4A7C15ull + ((uint64_t)c << 40) + ((uint64_t)q << 8) + (uint64_t)j;
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    const unsigned kind = (unsigned)(x & 3), uL = (unsigned)L, lo = uL / 2 > 40 ? 40 : 1, mid = uL / 2 > lo ? uL / 2 : lo;
+    const unsigned u = (unsigned)(x >> 8);
+    if (kind < 2) return (uint16_t)L;
+    if (kind == 2) return (uint16_t)(mid + u % (uL - mid + 1));
+    return (uint16_t)(lo + u % (mid - lo + 1));
+}
+
 /* batches in flight per sender (1..16; default 4): the back-pressure that bounds queueing latency */
 void bl_set_inflight(int batches) { g_inflight = batches < 1 ? 1 : batches > 16 ? 16 : batches; }
 
@@ -427,7 +453,10 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
     cpu_set_t saved, near;
     const int pinned = !sched_getaffinity(0, sizeof saved, &saved) && !near_cpus(device, &saved, &near) &&
                        !sched_setaffinity(0, sizeof near, &near);
-    pquic_fec_batch_cfg_t cfg = {device, batch_blocks, max_delay_us, (uint32_t)L, nstreams, g_poll_blocks};
+    const int ragged = g_ragged_max > 0;
+    if (ragged && g_ragged_max < L) return sender_fail(waits);
+    pquic_fec_batch_cfg_t cfg = {device, batch_blocks, max_delay_us, (uint32_t)(ragged ? g_ragged_max : L), nstreams,
+                                 g_poll_blocks};
     pquic_fec_batcher_t *b = pquic_fec_batcher_create(&cfg);
     if (!b) return sender_fail(waits);
     /* blocks in flight at most: every queued batch plus one being filled, per connection slot */
@@ -468,6 +497,13 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
     for (int c = 0; c < nconn; c++) {
         cnx[c].id = c;
         xorshift_fill(pool[c], (size_t)ppc * k * L, 0x5EEDF3C0 + (uint64_t)c * 0x9E3779B97F4A7C15ull);
+        /* ragged: a packet's row holds zeros past its length, so the pool's repairs (coded from whole rows
+         * below) are the repairs of the packets as sent */
+        for (long q = 0; ragged && q < ppc; q++)
+            for (int j = 0; j < k; j++) {
+                const uint16_t n = ragged_len(c, q, j, k, L);
+                memset(pool[c] + ((size_t)q * k + j) * L + n, 0, (size_t)L - n);
+            }
     }
     if (recover_e) {  /* the pool's repairs: each pool block q of connection c is block number c * ppc + q */
         fecgpu_host_ctx_t *hc = fecgpu_host_ctx_create(device, 2, (size_t)64 << 20);
@@ -505,6 +541,7 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
     long next_slot = 0;
     /* pass 0 warms up (pinned queue buffers allocated, device buffers grown), pass 1 is measured */
     uint64_t t0 = 0, t_wait = 0, t_submit = 0;
+    uint64_t payload = 0;  /* bytes in the measured pass's packets (ragged mode: the lost ones not counted) */
     long rec0 = 0;
     pquic_fec_batch_stats_t st0;
     memset(&st0, 0, sizeof st0);
@@ -521,6 +558,7 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
         t0 = now_us();
         const uint64_t t0s = stamp_us();
         t_wait = t_submit = 0;
+        payload = 0;
         int cur_c = 0, cur_lost = 0;
         long cur_q = 0, cur_round = 0;
         for (long blk = 0; blk < nb; blk++) {
@@ -558,7 +596,8 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
                 pquic_source_symbol_t *sym = &ss[si * k + j];
                 sym->fpid.raw = (fbn << 8) | (uint32_t)j;
                 sym->data = (uint8_t *)pb + (size_t)j * L;
-                sym->data_length = (uint16_t)L;
+                sym->data_length = ragged ? ragged_len(c, q, j, k, L) : (uint16_t)L;
+                payload += sym->data_length;
                 s->fb.source_symbols[j] = sym;
                 s->fb.current_source_symbols++;
             }
@@ -604,7 +643,7 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
         g_lat_q[6] = g_nlat ? sum / g_nlat : 0;
         g_lat_q[7] = (double)g_nlat;
     }
-    out[0] = nblocks * bytes_per_block / wall / 1073741824.0;
+    out[0] = (ragged ? (double)payload : nblocks * bytes_per_block) / wall / 1073741824.0;
     out[1] = g_nlat ? (double)g_lat[g_nlat / 2] : 0;
     out[2] = g_nlat ? (double)g_lat[(long)(g_nlat * 0.99)] : 0;
     out[3] = g_nlat ? (double)g_lat[g_nlat - 1] : 0;
