@@ -167,6 +167,34 @@ int fecgpu_rlc_decode_rows_len(const uint64_t *src_rows, const uint32_t *src_len
 int fecgpu_xor_encode(const void *src, void *rep, uint64_t nblocks, uint32_t k,
                       uint32_t symbol_size, void *stream);
 
+/* XOR on rows given by address, each of its own length, in one pass: no packed intermediate and no
+ * workspace.  src_rows[b * k + j] / src_len[b * k + j] are the address and length of source j of block b,
+ * rep_rows[b] ([nblocks]) the address of its one repair row and blk_len[b] the block's length (the
+ * reference's max_length).  The kernels clamp blk_len to symbol_size and src_len to blk_len, as the RLC
+ * *_rows_len forms do (the host forms check both before any launch).
+ * Encode writes exactly blk_len[b] bytes to the repair row: byte t is the XOR over j of source j's byte t,
+ * taken as 0 for t >= src_len (xor_fec_scheme_generate.c:51-73).
+ * Decode computes status[] and recovered[] exactly as fecgpu_xor_decode does from the masks clipped to k:
+ * RECOVERED iff popcount(sources present) + repair present == k and the repair is present, REF_UB when the
+ * sum holds with the repair absent, NOTHING otherwise; the bit of the missing index is set (also when the
+ * recovered bytes are all zero).  For a RECOVERED block exactly blk_len[b] bytes go to the missing source's
+ * own row, src_rows[b * k + miss]: the repair (read for blk_len[b] bytes) ^ the present sources, each read
+ * for min(src_len, blk_len[b]) bytes -- a received source longer than the block is truncated
+ * (xor_fec_scheme.c:54-70).  For any other status no row is read or written.
+ * Memory rules, those of the ragged copy kernels above: row addresses are 4-byte aligned, in device memory
+ * or mapped page-locked host memory; a row of 0 bytes is never dereferenced and its address may be 0, and
+ * so may that of an absent source or an absent repair; a load may touch the aligned dword that holds a
+ * row's last byte and nothing after it; stores are 16-B, then dword, then byte stores for the last 1-3
+ * bytes -- no dword is read-modify-written and nothing is written past blk_len[b].  The tables are
+ * device-accessible arrays.  k is 1..128, symbol_size a multiple of 4 from 4 to 65532.  Callers with packed
+ * rows keep fecgpu_xor_encode / fecgpu_xor_decode. */
+int fecgpu_xor_encode_rows(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                           const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t symbol_size, void *stream);
+int fecgpu_xor_decode_rows(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                           const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t symbol_size,
+                           const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                           uint64_t *recovered, void *stream);
+
 /* RLC decode.  Presence masks: bit j of src_present[2*b + j/64] set <=> source j of
  * block b was received; same for rep_present.  Recovered sources are written IN PLACE
  * into src[b][j]; bit j of recovered[2*b + j/64] is set for every source the reference
@@ -341,6 +369,19 @@ int fecgpu_xor_encode_host(fecgpu_host_ctx_t *ctx, const void *src, void *rep, u
 int fecgpu_xor_decode_host(fecgpu_host_ctx_t *ctx, void *src, const void *rep, uint64_t nblocks,
                            uint32_t k, uint32_t symbol_size, const uint64_t *src_present,
                            const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
+/* fecgpu_xor_encode_rows / fecgpu_xor_decode_rows from the host: the tables, masks, status and recovered
+ * are host arrays (page-locked ones are used in place, others are copied); the rows must be
+ * device-accessible.  The batch runs in sub-batches of about chunk_bytes of payload over the context's
+ * streams.  Before the context is looked at both check blk_len[b] <= symbol_size and src_len <= blk_len[b]
+ * (decode: for the sources present) and return FECGPU_ERR_INVALID otherwise, with nothing written.  Packed
+ * host rows keep fecgpu_xor_encode_host / fecgpu_xor_decode_host. */
+int fecgpu_xor_encode_rows_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint32_t *src_len,
+                                const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                uint32_t symbol_size);
+int fecgpu_xor_decode_rows_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint32_t *src_len,
+                                const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                uint32_t symbol_size, const uint64_t *src_present, const uint64_t *rep_present,
+                                uint8_t *status, uint64_t *recovered);
 
 /* ---- Resident single-block service (the synchronous hooks) ------------------------------------
  * One block per call, as the block framework calls fec_generate_repair_symbols / fec_recover

@@ -92,7 +92,14 @@ void pquic_fec_batcher_destroy(pquic_fec_batcher_t *b);
  * fecgpu_rlc_decode_rows_len_host), so only the bytes that exist cross PCIe, repairs and recovered
  * sources receive exactly the block's length, and only symbols outside every registered range are
  * staged.  (Against an engine library without those two entry points ragged blocks are staged,
- * zero-padded to the stride.)  Returns 0, or -1 (NULL / empty range, overlap with a registered range, registration failure). */
+ * zero-padded to the stride.)  XOR batches use the range the same way, through
+ * fecgpu_xor_encode_rows_host / fecgpu_xor_decode_rows_host (one pass, a length per row, whatever the
+ * lengths): generate reads the sources and writes the one repair where its symbol lies; recover reads
+ * the received sources and the repair and writes the recovered source into the symbol allocated at
+ * submission for the last missing index, with the XOR operation's FPID (fec_block_number << 8 | j), return
+ * value and counters (current_source_symbols stays as it was).  (Against an engine library without those
+ * two entry points XOR blocks are staged, packed and zero-padded.)
+ * Returns 0, or -1 (NULL / empty range, overlap with a registered range, registration failure). */
 int pquic_fec_batch_register_heap(pquic_fec_batcher_t *b, void *base, size_t bytes);
 /* Unregister the range registered at `base` (a connection closing).  No block whose symbols lie in it
  * may still be queued: the caller has had every done() for them.  Returns 0 or -1. */

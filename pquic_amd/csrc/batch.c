@@ -22,6 +22,11 @@
  * take a length per row, so every symbol in an arena is still handed over where it lies, for its own
  * length, and only symbols outside every arena are staged (at their own length, no padding).  Against an
  * engine without those two entry points (they are weak references) ragged blocks are staged as before.
+ * XOR jobs gather too: with a heap registered they run through fecgpu_xor_encode_rows_host /
+ * fecgpu_xor_decode_rows_host (one pass, a length per row, no equal-length arm), so every XOR symbol in an
+ * arena is read where it lies for its own length, the repair -- and on recover the symbol allocated at
+ * submission for the last missing source -- is written where it lies, and only symbols outside every arena
+ * are staged, unpadded.  Those two are weak references as well: an engine without them keeps XOR staged.
  * Windows (pquic_fec_batch_generate_window): the sliding-window sender protects the symbols in flight
  * once per window, so consecutive windows of a connection share most of their symbols, and every window
  * is block number 0, so all windows share their coefficients.  A window job therefore stages each
@@ -53,6 +58,12 @@
 #pragma weak fecgpu_rlc_decode_rows_len_host
 static int rows_len_available(void) {
     return fecgpu_rlc_encode_rows_len_host != NULL && fecgpu_rlc_decode_rows_len_host != NULL;
+}
+/* So are the XOR row forms: without them an XOR job is staged, packed and zero-padded, whatever is registered. */
+#pragma weak fecgpu_xor_encode_rows_host
+#pragma weak fecgpu_xor_decode_rows_host
+static int xor_rows_available(void) {
+    return fecgpu_xor_encode_rows_host != NULL && fecgpu_xor_decode_rows_host != NULL;
 }
 
 enum { OP_GENERATE = 0, OP_RECOVER = 1, OP_WINDOW = 2 /* generate, window blocks */ };
@@ -92,7 +103,7 @@ typedef struct job {
     int rc;
     int post;                      /* 1 once the engine ran: work items copy repairs out */
     uint32_t next_chunk, chunks_done;  /* staging work items claimed / finished (under the batcher lock) */
-    int gather;                    /* generate with row tables (fecgpu_rlc_encode_rows) */
+    int gather;                    /* row tables: RLC through the _rows / _rows_len forms, XOR through fecgpu_xor_*_rows_host */
     uint64_t *srow, *rrow;         /* pinned: [cap][k] source / [cap][r] repair row device addresses (recover:
                                     * a missing source's entry is the row its recovered bytes go to) */
     pquic_source_symbol_t **pre;   /* recover gather: [cap][k] symbols allocated at submission for the missing
@@ -310,8 +321,10 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
         if (!(j->seeds = fecgpu_host_alloc(eb))) return -1;
         j->seed_bytes = eb;
     }
-    /* gather tables (RLC generate or recover with a registered heap): grown on reuse like the repair table */
-    j->gather = (op == OP_GENERATE || op == OP_RECOVER) && !xor_scheme && __atomic_load_n(&b->nheaps, __ATOMIC_RELAXED) > 0;
+    /* gather tables (generate or recover with a registered heap; XOR where the engine has its row forms):
+     * grown on reuse like the repair table */
+    j->gather = (op == OP_GENERATE || op == OP_RECOVER) && (!xor_scheme || xor_rows_available()) &&
+                __atomic_load_n(&b->nheaps, __ATOMIC_RELAXED) > 0;
     if (j->gather && op == OP_RECOVER && j->pre_cap < (size_t)cap * k) {
         free(j->pre);
         j->pre_cap = (j->pre = calloc((size_t)cap * k, sizeof *j->pre)) ? (size_t)cap * k : 0;
@@ -335,7 +348,7 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
                       fecgpu_host_device_address(j->rep, rb ? rb : 4, &j->rep_dev) != FECGPU_OK))
         j->gather = 0;
     /* length tables of a gather job, where the engine takes them; without them the job stages ragged blocks */
-    if (j->gather && rows_len_available()) {
+    if (j->gather && (xor_scheme ? xor_rows_available() : rows_len_available())) {
         const size_t nr = (size_t)cap * (r ? r : 1);
         if (j->slen_cap < (size_t)cap * k) {
             fecgpu_host_free(j->slen);
@@ -350,6 +363,8 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
             j->blen_cap = (j->blen = fecgpu_host_alloc((size_t)cap * 4)) ? cap : 0;
         }
     }
+    /* the XOR row forms take a length per row and nothing else: no tables, no gather */
+    if (j->gather && xor_scheme && !(j->slen && j->rlen && j->blen)) j->gather = 0;
     j->ragged = 0;
     j->ncopy = 0;
     if (op == OP_WINDOW) {  /* window tables: start rows (page-locked), the stream's symbols, the grouping */
@@ -489,6 +504,11 @@ static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
     const uint32_t S = j->stride;
     if (j->op == OP_WINDOW)
         j->rc = fecgpu_rlc_window_encode_host(c, j->src, j->nrows, j->wrow, j->n, j->k, j->r, S, j->rep);
+    else if (j->gather && j->xor_scheme && j->op == OP_RECOVER)
+        j->rc = fecgpu_xor_decode_rows_host(c, j->srow, j->slen, j->rrow, j->blen, j->n, j->k, S, j->sp, j->rp, j->st,
+                                            j->rec);
+    else if (j->gather && j->xor_scheme)
+        j->rc = fecgpu_xor_encode_rows_host(c, j->srow, j->slen, j->rrow, j->blen, j->n, j->k, S);
     else if (j->gather && j->ragged && j->op == OP_RECOVER)
         j->rc = fecgpu_rlc_decode_rows_len_host(c, j->srow, j->slen, j->rrow, j->rlen, j->blen, j->n, j->k, j->r, S,
                                                 j->seeds, j->sp, j->rp, j->st, j->rec);
@@ -518,7 +538,9 @@ static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
  * length receives exactly that many bytes, and only symbols outside every heap are staged, at their own
  * length (the kernel zero-pads, :41-55).  A whole block's tables serve both forms: its lengths are the
  * stride.  Without length tables (an engine that takes none) a ragged block keeps the rule of before:
- * sources shorter than the block and repairs of blocks shorter than the stride are staged, zero-padded. */
+ * sources shorter than the block and repairs of blocks shorter than the stride are staged, zero-padded.
+ * An XOR job has one form only (fecgpu_xor_encode_rows_host, a length per row, one pass): every block of
+ * it takes the ragged arm, whatever its lengths. */
 static void gather_recover_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1);
 
 static void gather_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1) {
@@ -536,7 +558,7 @@ static void gather_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_
         const entry_t *e = &j->ent[i];
         const pquic_fec_block_t *fb = e->fb;
         if (lens) {
-            int whole = e->maxl == S;
+            int whole = !j->xor_scheme && e->maxl == S;
             for (uint32_t x = 0; whole && x < k; x++)
                 whole = fb->source_symbols[x] && fb->source_symbols[x]->data_length == S;
             j->blen[i] = e->maxl;
@@ -625,7 +647,9 @@ static void gather_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_
  * the stride, is ragged instead and marks the job so: each received symbol that lies in a heap for
  * min(its length, max_length) bytes is read in place for that many, each symbol allocated for a missing
  * source that lies in one for max_length bytes receives exactly that many, and only symbols outside every
- * heap are staged, at that length without padding.  A whole block's lengths are the stride. */
+ * heap are staged, at that length without padding.  A whole block's lengths are the stride.
+ * An XOR job (fecgpu_xor_decode_rows_host) takes the ragged arm for every block: its one repair row, and
+ * the one symbol allocated at submission for the last missing source. */
 static void gather_recover_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1) {
     const uint32_t S = j->stride, k = j->k, r = j->r;
     const int lens = j->slen && j->rlen && j->blen;
@@ -639,7 +663,7 @@ static void gather_recover_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0,
         uint64_t *sp = j->sp + 2 * (size_t)i, *rp = j->rp + 2 * (size_t)i, *cpm = j->cpm + 2 * (size_t)i;
         sp[0] = sp[1] = rp[0] = rp[1] = cpm[0] = cpm[1] = 0;
         if (lens) {
-            int full = whole;  /* every received symbol reaches the stride */
+            int full = whole && !j->xor_scheme;  /* every received symbol reaches the stride */
             for (uint32_t x = 0; full && x < k; x++)
                 full = !fb->source_symbols[x] || fb->source_symbols[x]->data_length >= S;
             for (uint32_t x = 0; full && x < r; x++)
@@ -1142,7 +1166,9 @@ static int submit(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t
     j->ent[i] = (entry_t){cnx, fb, done, user, maxl, -1};
     if (GENERATES(op))  /* the protocol operation's allocations, in its order, on this thread */
         j->ent[i].nalloc = (int16_t)fec_generate_alloc(cnx, fb, maxl, j->reps + (size_t)i * r);
-    else if (j->gather)  /* the recovered symbols, so the kernel writes them where they will stay */
+    else if (j->gather && xor_scheme)  /* the one recovered symbol, so the kernel writes it where it will stay */
+        fec_recover_alloc_xor(cnx, fb, maxl, j->pre + (size_t)i * k);
+    else if (j->gather)  /* the recovered symbols, likewise */
         fec_recover_alloc(cnx, fb, maxl, j->pre + (size_t)i * k);
     if (!i) {
         j->t_first = now_us;
@@ -1297,6 +1323,10 @@ static int collect(pquic_fec_batcher_t *b, uint32_t budget) {
                     }
             } else if (GENERATES(j->op)) {
                 ret = fec_generate_attach(e->fb, reps, e->nalloc);
+            } else if (pre && j->xor_scheme) {
+                ret = fec_recover_finish_pre_xor(e->cnx, e->fb, j->st[i], j->rec + 2 * (size_t)i, pre,
+                                                 j->cpm + 2 * (size_t)i, j->src + (size_t)i * j->k * S, S, e->maxl,
+                                                 &nrec);
             } else if (pre) {
                 /* rows the kernel wrote into the staging area (no in-place row for them) are copied */
                 ret = fec_recover_finish_pre(e->cnx, e->fb, j->st[i], j->rec + 2 * (size_t)i, pre,

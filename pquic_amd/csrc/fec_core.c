@@ -230,3 +230,44 @@ protoop_arg_t fec_recover_finish_pre(picoquic_cnx_t *cnx, pquic_fec_block_t *fb,
     *nrec_acc += nrec;
     return 0;
 }
+
+int fec_recover_alloc_xor(picoquic_cnx_t *cnx, const pquic_fec_block_t *fb, uint16_t maxl, pquic_source_symbol_t **pre) {
+    int last = -1;
+    for (int j = 0; j < fb->total_source_symbols; j++) {
+        pre[j] = NULL;
+        if (!fb->source_symbols[j]) last = j;  /* the LAST missing index (xor_fec_scheme.c:54-58) */
+    }
+    if (last < 0) return 0;
+    pre[last] = new_source(cnx, (fb->fec_block_number << 8) | (uint32_t)last, maxl);
+    return pre[last] != NULL;
+}
+
+protoop_arg_t fec_recover_finish_pre_xor(picoquic_cnx_t *cnx, pquic_fec_block_t *fb, uint8_t status,
+                                         const uint64_t rec[2], pquic_source_symbol_t *const *pre,
+                                         const uint64_t copy[2], const uint8_t *src_rows, uint32_t stride,
+                                         uint16_t maxl, uint64_t *nrec_acc) {
+    const int k = fb->total_source_symbols;
+    if (status == FECGPU_BLOCK_REF_UB) FEC_STAT_ADD(ref_ub_blocks, 1);
+    for (int j = 0; j < k; j++) {  /* a pre-allocation the engine did not fill goes back first */
+        const int got = status == FECGPU_BLOCK_RECOVERED && ((rec[j >> 6] >> (j & 63)) & 1);
+        if (!got && pre[j]) {
+            g_fec_api.my_free(cnx, pre[j]->data);
+            g_fec_api.my_free(cnx, pre[j]);
+        }
+    }
+    protoop_arg_t ret = 1;
+    for (int j = 0; j < k && status == FECGPU_BLOCK_RECOVERED; j++) {
+        if (!((rec[j >> 6] >> (j & 63)) & 1)) continue;
+        pquic_source_symbol_t *ss = pre[j];
+        if (!ss) {  /* its pre-allocation had failed: allocate as fec_recover_finish does */
+            if (!(ss = new_source(cnx, (fb->fec_block_number << 8) | (uint32_t)j, maxl))) return PQUIC_ERROR_MEMORY;
+            memcpy(ss->data, src_rows + (size_t)j * stride, maxl);
+        } else if ((copy[j >> 6] >> (j & 63)) & 1) {
+            memcpy(ss->data, src_rows + (size_t)j * stride, maxl);
+        }
+        fb->source_symbols[j] = ss;  /* current_source_symbols is NOT incremented (:72) */
+        ++*nrec_acc;
+        ret = 0;
+    }
+    return ret;
+}

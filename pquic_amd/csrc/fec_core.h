@@ -89,6 +89,20 @@ protoop_arg_t fec_recover_finish_pre(picoquic_cnx_t *cnx, pquic_fec_block_t *fb,
                                      pquic_source_symbol_t *const *pre, const uint64_t copy[2], const uint8_t *src_rows,
                                      uint32_t stride, uint16_t maxl, uint64_t *nrec_acc);
 
+/* The XOR counterparts (the batcher's XOR gather jobs).  fec_recover_alloc_xor allocates one symbol of maxl
+ * bytes for the LAST missing source j -- the one xor_fec_scheme.c:54-58 recovers -- with the XOR branch's
+ * FPID, (fec_block_number << 8) | j, into pre[j]; every other pre[] entry is NULL.  Returns how many it got
+ * (0 or 1).  fec_recover_finish_pre_xor keeps fec_recover_finish's XOR semantics: the recovered source is
+ * inserted (pre[j]; copied from src_rows row j first when bit j of `copy` is set; allocated anew and copied
+ * when the pre-allocation had failed, PQUIC_ERROR_MEMORY when that fails too), current_source_symbols is
+ * NOT incremented (:72), the symbol is counted once into *nrec_acc, and the value is 0; when nothing was
+ * recovered the pre-allocation is freed and the value is 1. */
+int fec_recover_alloc_xor(picoquic_cnx_t *cnx, const pquic_fec_block_t *fb, uint16_t maxl, pquic_source_symbol_t **pre);
+protoop_arg_t fec_recover_finish_pre_xor(picoquic_cnx_t *cnx, pquic_fec_block_t *fb, uint8_t status,
+                                         const uint64_t rec[2], pquic_source_symbol_t *const *pre,
+                                         const uint64_t copy[2], const uint8_t *src_rows, uint32_t stride,
+                                         uint16_t maxl, uint64_t *nrec_acc);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus

@@ -23,6 +23,7 @@
 //   k_xor_*        XOR scheme, streaming 16-B lanes.
 //   k_rows_gather / k_rows_scatter   ragged rows (a length per row) to and from a packed batch, around
 //                  the packed encode / decode: the *_rows_len entry points.
+//   k_xor_encode_rows / k_xor_decode_rows   XOR on rows given by address, a length per row, in one pass.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -3342,6 +3343,215 @@ __global__ __launch_bounds__(256) void k_rows_scatter(const uint8_t *__restrict_
 }
 
 // =============================================================================================
+// XOR on rows (fecgpu_xor_encode_rows / fecgpu_xor_decode_rows): one pass, no packed intermediate.  A
+// team of FEC_XOR_ROWS_LPB lanes codes one block, 16 B per lane and step: it XORs the block's input rows
+// -- encode: the k sources; decode: the k - 1 present sources and the repair -- each read for its own
+// length (zeros past it), and stores exactly blk_len bytes to the output row (the repair; the missing
+// source).  The block's addresses and lengths are read once: into registers when k is fixed at compile
+// time (KC > 0: 2..8 and 16, as the packed kernels), else into LDS.  Loads and stores follow the rules
+// of the ragged copy kernels above.
+// =============================================================================================
+// Lanes per block: profiles/xor_rows.log (A/B builds define another; FEC_XOR_ROWS_KC=0 builds send every k
+// through the LDS tables).
+#ifndef FEC_XOR_ROWS_LPB
+#define FEC_XOR_ROWS_LPB 32
+#endif
+#ifndef FEC_XOR_ROWS_KC
+#define FEC_XOR_ROWS_KC 1
+#endif
+
+// dwords [w, w + 4) of an input row of n bytes: bytes past n read as zeros, a row of 0 bytes is never
+// dereferenced, the last 1-3 bytes come from the aligned dword that holds them
+__device__ __forceinline__ rows_u32x4 xor_rows_load(uint64_t addr, uint32_t n, int w) {
+  rows_u32x4 v = {0u, 0u, 0u, 0u};
+  const int nd = (int)(n >> 2), t = (int)(n & 3);
+  const ROWS_GLOBAL uint32_t *a = (const ROWS_GLOBAL uint32_t *)addr;
+  if (w + 4 <= nd) {
+    v = *(const ROWS_GLOBAL rows_u32x4_a4 *)(a + w);
+  } else if ((uint32_t)w * 4u < n) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      if (w + i < nd) v[i] = a[w + i];
+      else if (w + i == nd && t) v[i] = a[nd] & ((1u << (8 * t)) - 1u);
+    }
+  }
+  return v;
+}
+
+// the XOR of dwords [w, w + 4) of N input rows.  Two phases, so the loads are in flight together: first the
+// 16-B load of every row the column lies inside, then the rows the column ends in (rare, dword by dword).
+// Used for the compile-time k of 16 only: profiles/xor_rows.log.
+template <int N>
+__device__ __forceinline__ rows_u32x4 xor_rows_load_n(const uint64_t *a, const uint32_t *n, int w) {
+  rows_u32x4 v[N];
+#pragma unroll
+  for (int j = 0; j < N; j++) {
+    v[j] = rows_u32x4{0u, 0u, 0u, 0u};
+    if (w + 4 <= (int)(n[j] >> 2)) v[j] = *(const ROWS_GLOBAL rows_u32x4_a4 *)((const ROWS_GLOBAL uint32_t *)a[j] + w);
+  }
+#pragma unroll
+  for (int j = 0; j < N; j++)
+    if (w + 4 > (int)(n[j] >> 2) && (uint32_t)w * 4u < n[j]) v[j] = xor_rows_load(a[j], n[j], w);
+  rows_u32x4 acc = v[0];
+#pragma unroll
+  for (int j = 1; j < N; j++) acc ^= v[j];
+  return acc;
+}
+
+// dwords [w, w + 4) of an output row of n bytes (w * 4 < n): a 16-B store, else dword stores, then byte
+// stores for the last 1-3 bytes; nothing at or past byte n
+__device__ __forceinline__ void xor_rows_store(uint64_t addr, uint32_t n, int w, rows_u32x4 v) {
+  const int nd = (int)(n >> 2), t = (int)(n & 3);
+  ROWS_GLOBAL uint32_t *a = (ROWS_GLOBAL uint32_t *)addr;
+  if (w + 4 <= nd) {
+    *(ROWS_GLOBAL rows_u32x4_a4 *)(a + w) = v;
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if (w + i < nd) {
+      a[w + i] = v[i];
+    } else if (w + i == nd && t) {
+      ROWS_GLOBAL uint8_t *tail = (ROWS_GLOBAL uint8_t *)(a + nd);
+      for (int x = 0; x < t; x++) tail[x] = (uint8_t)(v[i] >> (8 * x));
+    }
+  }
+}
+
+// status and the missing index of block b from its masks clipped to k, as k_xor_decode
+__device__ __forceinline__ int xor_rows_status(const uint64_t *sp, const uint64_t *rp, uint64_t b, int k, int *miss) {
+  uint64_t s0 = sp[2 * b], s1 = sp[2 * b + 1];
+  if (k < 64) { s0 &= (1ull << k) - 1; s1 = 0; } else if (k < 128) s1 &= (1ull << ((k - 64) & 63)) - 1;
+  const int cur_rs = (int)(rp[2 * b] & 1);
+  *miss = -1;
+  if (__popcll(s0) + __popcll(s1) + cur_rs != k) return FECGPU_BLOCK_NOTHING;
+  if (!cur_rs) return FECGPU_BLOCK_REF_UB;
+  uint64_t m0 = ~s0, m1 = ~s1;
+  if (k < 64) { m0 &= (1ull << k) - 1; m1 = 0; } else if (k < 128) m1 &= (1ull << ((k - 64) & 63)) - 1;
+  *miss = m1 ? 127 - __clzll(m1) : 63 - __clzll(m0);  // the one missing source (xor_fec_scheme.c:54-58)
+  return FECGPU_BLOCK_RECOVERED;
+}
+
+// The body of both kernels.  DEC: decode (masks, status, recovered; the output row is the missing source's).
+template <int KC, bool DEC, int LPB>
+__device__ __forceinline__ void xor_rows_body(const uint64_t *__restrict__ src_rows,
+                                              const uint32_t *__restrict__ src_len,
+                                              const uint64_t *__restrict__ rep_rows,
+                                              const uint32_t *__restrict__ blk_len, uint64_t nblocks, int k_rt, int L,
+                                              const uint64_t *__restrict__ sp, const uint64_t *__restrict__ rp,
+                                              uint8_t *__restrict__ status, uint64_t *__restrict__ recovered) {
+  constexpr int BPW = 256 / LPB;       // blocks per workgroup and step
+  constexpr int KR = KC ? KC : 1;      // register entries
+  constexpr int KS = KC ? 1 : FECGPU_MAX_K;  // LDS entries per team
+  __shared__ uint64_t s_a[BPW][KS];
+  __shared__ uint32_t s_n[BPW][KS];
+  const int k = KC ? KC : k_rt;
+  const int team = threadIdx.x / LPB, sub = threadIdx.x % LPB;
+  // every team of the workgroup takes the same number of steps (the LDS path has barriers in them)
+  for (uint64_t b0 = (uint64_t)blockIdx.x * BPW; b0 < nblocks; b0 += (uint64_t)gridDim.x * BPW) {
+    const uint64_t b = b0 + (uint32_t)team;
+    const bool live = b < nblocks;
+    uint32_t nb = live ? blk_len[b] : 0u;
+    if (nb > (uint32_t)L) nb = (uint32_t)L;
+    int miss = -1;
+    if (DEC && live) {
+      const int st = xor_rows_status(sp, rp, b, k, &miss);
+      if (sub == 0) {
+        status[b] = (uint8_t)st;
+        recovered[2 * b] = miss >= 0 && miss < 64 ? 1ull << miss : 0;
+        recovered[2 * b + 1] = miss >= 64 ? 1ull << (miss - 64) : 0;
+      }
+      if (st != FECGPU_BLOCK_RECOVERED) nb = 0;  // no row is read or written
+    }
+    // the block's m inputs: the sources (decode: but the missing one), then for decode the repair
+    const int m = nb ? k : 0;
+    const uint64_t out = !nb ? 0 : DEC ? src_rows[b * (uint32_t)k + (uint32_t)miss] : rep_rows[b];
+    uint64_t a[KR];
+    uint32_t n[KR];
+    uint32_t nmin = nb;  // every input reaches byte nmin
+    if (KC) {
+#pragma unroll
+      for (int j = 0; j < KR; j++) {
+        const int q = DEC ? j + (j >= miss) : j;  // source index; k: the repair
+        a[j] = 0;
+        n[j] = 0;
+        if (nb) {
+          const bool rep = DEC && q >= k;
+          n[j] = rep ? nb : src_len[b * (uint32_t)k + (uint32_t)q];
+          if (n[j] > nb) n[j] = nb;
+          if (n[j]) a[j] = rep ? rep_rows[b] : src_rows[b * (uint32_t)k + (uint32_t)q];
+          if (n[j] < nmin) nmin = n[j];
+        }
+      }
+    } else {
+      __syncthreads();  // the previous step's reads of the team's entries
+      for (int j = sub; j < m; j += LPB) {
+        const int q = DEC ? j + (j >= miss) : j;
+        const bool rep = DEC && q >= k;
+        uint32_t x = rep ? nb : src_len[b * (uint32_t)k + (uint32_t)q];
+        if (x > nb) x = nb;
+        s_n[team][j] = x;
+        s_a[team][j] = !x ? 0 : rep ? rep_rows[b] : src_rows[b * (uint32_t)k + (uint32_t)q];
+        if (x < nmin) nmin = x;
+      }
+#pragma unroll
+      for (int o = LPB / 2; o; o >>= 1) {  // the team's minimum (LPB lanes of one wave)
+        const uint32_t y = (uint32_t)__shfl_xor((int)nmin, o, LPB);
+        if (y < nmin) nmin = y;
+      }
+      __syncthreads();
+    }
+    const int wfull = (int)(nmin >> 2);
+    for (int w = sub * 4; (uint32_t)w * 4u < nb; w += LPB * 4) {
+      rows_u32x4 acc = {0u, 0u, 0u, 0u};
+      if (KC) {
+        if (w + 4 <= wfull) {  // inside every input: the loads back to back
+          rows_u32x4 v[KR];
+#pragma unroll
+          for (int j = 0; j < KR; j++) v[j] = *(const ROWS_GLOBAL rows_u32x4_a4 *)((const ROWS_GLOBAL uint32_t *)a[j] + w);
+#pragma unroll
+          for (int j = 0; j < KR; j++) acc ^= v[j];
+        } else if (KR >= 16) {  // many rows: their loads together (k16 ragged 578 -> 369 us; k4 lost, 97 -> 166)
+          acc = xor_rows_load_n<KR>(a, n, w);
+        } else {
+#pragma unroll
+          for (int j = 0; j < KR; j++) acc ^= xor_rows_load(a[j], n[j], w);
+        }
+      } else if (w + 4 <= wfull) {
+#pragma unroll 4
+        for (int j = 0; j < m; j++) acc ^= *(const ROWS_GLOBAL rows_u32x4_a4 *)((const ROWS_GLOBAL uint32_t *)s_a[team][j] + w);
+      } else {
+        for (int j = 0; j < m; j++) acc ^= xor_rows_load(s_a[team][j], s_n[team][j], w);
+      }
+      xor_rows_store(out, nb, w, acc);
+    }
+  }
+}
+
+// xor_fec_scheme_generate.c:51-73 on rows: rep_rows[b] receives blk_len[b] bytes, the XOR of the k sources
+template <int KC, int LPB>
+__global__ __launch_bounds__(256) void k_xor_encode_rows(const uint64_t *__restrict__ src_rows,
+                                                         const uint32_t *__restrict__ src_len,
+                                                         const uint64_t *__restrict__ rep_rows,
+                                                         const uint32_t *__restrict__ blk_len, uint64_t nblocks, int k,
+                                                         int L) {
+  xor_rows_body<KC, false, LPB>(src_rows, src_len, rep_rows, blk_len, nblocks, k, L, nullptr, nullptr, nullptr, nullptr);
+}
+
+// xor_fec_scheme.c:41-74 on rows: status and recovered as k_xor_decode; a RECOVERED block's missing source
+// row receives blk_len[b] bytes, the repair ^ the present sources (each truncated to blk_len[b])
+template <int KC, int LPB>
+__global__ __launch_bounds__(256) void k_xor_decode_rows(const uint64_t *__restrict__ src_rows,
+                                                         const uint32_t *__restrict__ src_len,
+                                                         const uint64_t *__restrict__ rep_rows,
+                                                         const uint32_t *__restrict__ blk_len, uint64_t nblocks, int k,
+                                                         int L, const uint64_t *__restrict__ sp,
+                                                         const uint64_t *__restrict__ rp, uint8_t *__restrict__ status,
+                                                         uint64_t *__restrict__ recovered) {
+  xor_rows_body<KC, true, LPB>(src_rows, src_len, rep_rows, blk_len, nblocks, k, L, sp, rp, status, recovered);
+}
+
+// =============================================================================================
 // Launch configuration
 // =============================================================================================
 static int pick_rt(uint32_t r) { return r >= 16 ? 16 : r >= 8 ? 8 : r >= 4 ? 4 : r >= 2 ? 2 : 1; }
@@ -3840,6 +4050,69 @@ int fecgpu_rows_scatter(const void *src, const uint64_t *rows, const uint32_t *l
                         uint32_t symbol_size, void *stream) {
   if (int rc = rows_args(rows, len, src, nrows, symbol_size)) return rc;
   return launch_scatter(src, rows, len, nrows, symbol_size, nullptr, nullptr, nullptr, 1, 0, (hipStream_t)stream);
+}
+
+// ---- XOR on rows ----
+// k = 2..8 and 16 get a compile-time row count (their tables in registers); other k keep them in LDS.
+extern "C++" {
+template <bool DEC, typename... A>
+static void xor_rows_launch(uint32_t k, uint64_t nblocks, hipStream_t s, A... a) {
+  constexpr int LPB = FEC_XOR_ROWS_LPB;
+  constexpr uint64_t bpw = 256 / LPB;
+  const uint64_t wgs = (nblocks + bpw - 1) / bpw;
+  const dim3 grid((uint32_t)(wgs < 65536 ? wgs : 65536));  // grid-stride beyond, on a 64-bit block index
+#define XOR_ROWS_GO(KC)                                                                            \
+  if constexpr (DEC) hipLaunchKernelGGL((k_xor_decode_rows<KC, LPB>), grid, dim3(256), 0, s, a...); \
+  else hipLaunchKernelGGL((k_xor_encode_rows<KC, LPB>), grid, dim3(256), 0, s, a...);              \
+  break;
+  switch (FEC_XOR_ROWS_KC ? k : 0) {
+    case 2: XOR_ROWS_GO(2)
+    case 3: XOR_ROWS_GO(3)
+    case 4: XOR_ROWS_GO(4)
+    case 5: XOR_ROWS_GO(5)
+    case 6: XOR_ROWS_GO(6)
+    case 7: XOR_ROWS_GO(7)
+    case 8: XOR_ROWS_GO(8)
+    case 16: XOR_ROWS_GO(16)
+    default: XOR_ROWS_GO(0)
+  }
+#undef XOR_ROWS_GO
+}
+}  // extern "C++"
+
+static int xor_rows_args(const void *src_rows, const void *src_len, const void *rep_rows, const void *blk_len,
+                         uint32_t k, uint32_t L) {
+  if (!src_rows || !src_len || !rep_rows || !blk_len) return set_err(FECGPU_ERR_INVALID, "%s", "NULL row / length table");
+  if (k < 1 || k > FECGPU_MAX_K) return set_err(FECGPU_ERR_INVALID, "%s", "k out of range [1,128]");
+  if (L == 0 || (L & 3) || L > 65532) return set_err(FECGPU_ERR_INVALID, "%s", "symbol_size must be a positive multiple of 4 (<= 65532)");
+  return FECGPU_OK;
+}
+
+int fecgpu_xor_encode_rows(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                           const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t symbol_size, void *stream) {
+  int rc = xor_rows_args(src_rows, src_len, rep_rows, blk_len, k, symbol_size);
+  if (rc || nblocks == 0) return rc;
+  xor_rows_launch<false>(k, nblocks, (hipStream_t)stream, src_rows, src_len, rep_rows, blk_len, nblocks, (int)k,
+                         (int)symbol_size);
+  HIPCHK(hipGetLastError());
+  count_encode(nblocks);
+  return FECGPU_OK;
+}
+
+int fecgpu_xor_decode_rows(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                           const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t symbol_size,
+                           const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                           uint64_t *recovered, void *stream) {
+  int rc = xor_rows_args(src_rows, src_len, rep_rows, blk_len, k, symbol_size);
+  if (rc) return rc;
+  if (!src_present || !rep_present || !status || !recovered)
+    return set_err(FECGPU_ERR_INVALID, "%s", "NULL mask/status");
+  if (nblocks == 0) return FECGPU_OK;
+  xor_rows_launch<true>(k, nblocks, (hipStream_t)stream, src_rows, src_len, rep_rows, blk_len, nblocks, (int)k,
+                        (int)symbol_size, src_present, rep_present, status, recovered);
+  HIPCHK(hipGetLastError());
+  count_decode(nblocks);
+  return FECGPU_OK;
 }
 
 // the packed arrays of one pass, each from a 256-B boundary, then the decode workspace

@@ -791,6 +791,122 @@ int fecgpu_rlc_decode_rows_len_host(fecgpu_host_ctx_t *c, const uint64_t *src_ro
   return finish(c, rc);
 }
 
+// ---- XOR on rows (fecgpu_xor_encode_rows_host / fecgpu_xor_decode_rows_host) ----
+// One pass and no packed arrays: a sub-batch needs nothing of its slot but the stream.
+int fecgpu_xor_encode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                uint32_t L) {
+  if (!src_rows || !src_len || !rep_rows || !blk_len) return rows_len_invalid("NULL row / length table");
+  if (int rc = rows_len_shape(k, 1, L)) return rc;
+  if (int rc = rows_len_check(src_len, blk_len, nullptr, nblocks, k, L)) return rc;
+  if (!c) return rows_len_invalid("NULL host context");
+  if (!nblocks) return FECGPU_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HCHK(hipSetDevice(c->device));
+  Slot &s = c->slot[0];
+  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
+  const uint64_t *dr = ds ? (const uint64_t *)mapped_host(rep_rows, nblocks * 8) : nullptr;
+  const uint32_t *dsl = dr ? (const uint32_t *)mapped_host(src_len, nblocks * k * 4) : nullptr;
+  const uint32_t *dbl = dsl ? (const uint32_t *)mapped_host(blk_len, nblocks * 4) : nullptr;
+  const bool in_place = dbl != nullptr;
+  int rc = FECGPU_OK;
+  do {
+    if (!in_place) {  // pageable tables: one device copy, and the whole batch on this slot's stream
+      const size_t o_rep = nblocks * k * 8, o_sl = o_rep + nblocks * 8, o_bl = o_sl + nblocks * k * 4;
+      LCHK(grow(&s.d_aux, &s.cap_aux, o_bl + nblocks * 4));
+      uint8_t *a = (uint8_t *)s.d_aux;
+      LCHK(hipMemcpyAsync(a, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync(a + o_rep, rep_rows, nblocks * 8, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync(a + o_sl, src_len, nblocks * k * 4, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync(a + o_bl, blk_len, nblocks * 4, hipMemcpyHostToDevice, s.st));
+      ds = (const uint64_t *)a;
+      dr = (const uint64_t *)(a + o_rep);
+      dsl = (const uint32_t *)(a + o_sl);
+      dbl = (const uint32_t *)(a + o_bl);
+    }
+    Pacer pc(c, nblocks, (size_t)(k + 1) * L);  // hooks in use: slices that yield to them
+    if (!in_place) pc.slice = 0;
+    const uint64_t step = pc.slice ? pc.slice : sub_batch(c, nblocks, (size_t)(k + 1) * L);
+    int si = 0;
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += step) {
+      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
+      LCHK(pc.before());
+      Slot &w = c->slot[pc.slice ? pc.n % pc.streams : si];
+      if ((rc = fecgpu_xor_encode_rows(ds + b0 * k, dsl + b0 * k, dr + b0, dbl + b0, m, k, L, w.st))) break;
+      LCHK(pc.after());
+      if (in_place) si = (si + 1) % c->ns;
+    }
+  } while (0);
+  return finish(c, rc);
+}
+
+int fecgpu_xor_decode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                uint32_t L, const uint64_t *sp, const uint64_t *rp, uint8_t *status,
+                                uint64_t *recovered) {
+  if (!src_rows || !src_len || !rep_rows || !blk_len) return rows_len_invalid("NULL row / length table");
+  if (!sp || !rp || !status || !recovered) return rows_len_invalid("NULL mask/status");
+  if (int rc = rows_len_shape(k, 1, L)) return rc;
+  if (int rc = rows_len_check(src_len, blk_len, sp, nblocks, k, L)) return rc;
+  if (!c) return rows_len_invalid("NULL host context");
+  if (!nblocks) return FECGPU_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HCHK(hipSetDevice(c->device));
+  Slot &s = c->slot[0];
+  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
+  const uint32_t *dsl = ds ? (const uint32_t *)mapped_host(src_len, nblocks * k * 4) : nullptr;
+  const uint32_t *dbl = dsl ? (const uint32_t *)mapped_host(blk_len, nblocks * 4) : nullptr;
+  const uint64_t *dr = dbl ? (const uint64_t *)mapped_host(rep_rows, nblocks * 8) : nullptr;
+  const uint64_t *dsp = dr ? (const uint64_t *)mapped_host(sp, nblocks * 16) : nullptr;
+  const uint64_t *drp = dsp ? (const uint64_t *)mapped_host(rp, nblocks * 16) : nullptr;
+  uint8_t *dst = drp ? mapped_host(status, nblocks) : nullptr;
+  uint64_t *drec = dst ? (uint64_t *)mapped_host(recovered, nblocks * 16) : nullptr;
+  const bool in_place = drec != nullptr;
+  int rc = FECGPU_OK;
+  do {
+    if (!in_place) {  // pageable: one device copy of the tables and masks, the whole batch on this slot's stream
+      const size_t o_rep = nblocks * k * 8, o_m = o_rep + nblocks * 8, o_sl = o_m + nblocks * 48,
+                   o_bl = o_sl + nblocks * k * 4, o_st = o_bl + nblocks * 4;
+      LCHK(grow(&s.d_aux, &s.cap_aux, o_st + nblocks));
+      uint8_t *a = (uint8_t *)s.d_aux;
+      ds = (const uint64_t *)a;
+      dr = (const uint64_t *)(a + o_rep);
+      uint64_t *mk = (uint64_t *)(a + o_m);
+      dsp = mk;
+      drp = mk + 2 * nblocks;
+      drec = mk + 4 * nblocks;
+      dsl = (const uint32_t *)(a + o_sl);
+      dbl = (const uint32_t *)(a + o_bl);
+      dst = a + o_st;
+      LCHK(hipMemcpyAsync((void *)ds, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync((void *)dr, rep_rows, nblocks * 8, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync((void *)dsl, src_len, nblocks * k * 4, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync((void *)dbl, blk_len, nblocks * 4, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync((void *)dsp, sp, nblocks * 16, hipMemcpyHostToDevice, s.st));
+      LCHK(hipMemcpyAsync((void *)drp, rp, nblocks * 16, hipMemcpyHostToDevice, s.st));
+    }
+    Pacer pc(c, nblocks, (size_t)(k + 1) * L);  // hooks in use: slices that yield to them
+    if (!in_place) pc.slice = 0;
+    const uint64_t step = pc.slice ? pc.slice : sub_batch(c, nblocks, (size_t)(k + 1) * L);
+    int si = 0;
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += step) {
+      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
+      LCHK(pc.before());
+      Slot &w = c->slot[pc.slice ? pc.n % pc.streams : si];
+      if ((rc = fecgpu_xor_decode_rows(ds + b0 * k, dsl + b0 * k, dr + b0, dbl + b0, m, k, L, dsp + 2 * b0,
+                                       drp + 2 * b0, dst + b0, drec + 2 * b0, w.st)))
+        break;
+      LCHK(pc.after());
+      if (in_place) si = (si + 1) % c->ns;
+    }
+    if (rc == FECGPU_OK && !in_place) {
+      LCHK(hipMemcpyAsync(status, dst, nblocks, hipMemcpyDeviceToHost, s.st));
+      LCHK(hipMemcpyAsync(recovered, drec, nblocks * 16, hipMemcpyDeviceToHost, s.st));
+    }
+  } while (0);
+  return finish(c, rc);
+}
+
 int fecgpu_xor_decode_host(fecgpu_host_ctx_t *c, void *src, const void *rep, uint64_t nblocks, uint32_t k,
                            uint32_t L, const uint64_t *sp, const uint64_t *rp, uint8_t *status,
                            uint64_t *recovered) {

@@ -109,6 +109,11 @@ def load_library(path: str = LIB_PATH, private: bool = False):
         L.fecgpu_rlc_decode_rows_len.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v, v, sz, v]
         L.fecgpu_rlc_encode_rows_len_host.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v]
         L.fecgpu_rlc_decode_rows_len_host.argtypes = [v, v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v]
+    if hasattr(L, "fecgpu_xor_encode_rows"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
+        L.fecgpu_xor_encode_rows.argtypes = [v, v, v, v, u64, u32, u32, v]
+        L.fecgpu_xor_decode_rows.argtypes = [v, v, v, v, u64, u32, u32, v, v, v, v, v]
+        L.fecgpu_xor_encode_rows_host.argtypes = [v, v, v, v, v, u64, u32, u32]
+        L.fecgpu_xor_decode_rows_host.argtypes = [v, v, v, v, v, u64, u32, u32, v, v, v, v]
     if not private:
         _lib = L
     return L
@@ -390,6 +395,23 @@ class Engine:
             _addr(workspace), workspace.numel(), self._stream(stream)), "fecgpu_rlc_decode_rows_len")
         return status, recovered
 
+    def xor_encode_rows(self, src_rows, src_len, rep_rows, blk_len, nblocks: int, k: int, L: int, stream=None):
+        """fecgpu_xor_encode_rows: one pass over rows given by address (u64 tables) and length (u32);
+        rep_rows[b] receives exactly blk_len[b] bytes."""
+        self._check(self.lib.fecgpu_xor_encode_rows(_addr(src_rows), _addr(src_len), _addr(rep_rows),
+                                                    _addr(blk_len), nblocks, k, L, self._stream(stream)),
+                    "fecgpu_xor_encode_rows")
+
+    def xor_decode_rows(self, src_rows, src_len, rep_rows, blk_len, src_present, rep_present, status, recovered,
+                        nblocks: int, k: int, L: int, stream=None):
+        """fecgpu_xor_decode_rows: the missing source of a RECOVERED block receives exactly blk_len[b] bytes at
+        its own row, src_rows[b*k+miss]."""
+        self._check(self.lib.fecgpu_xor_decode_rows(_addr(src_rows), _addr(src_len), _addr(rep_rows),
+                                                    _addr(blk_len), nblocks, k, L, _addr(src_present),
+                                                    _addr(rep_present), _addr(status), _addr(recovered),
+                                                    self._stream(stream)), "fecgpu_xor_decode_rows")
+        return status, recovered
+
     def synth_fill(self, dst, nbytes: int, seed: int, offset: int = 0, stream=None):
         self._check(self.lib.fecgpu_synth_fill(_addr(dst), nbytes, seed, offset, self._stream(stream)),
                     "fecgpu_synth_fill")
@@ -455,3 +477,14 @@ class HostPath:
                                                            nblocks, k, r, L, _addr(seeds), _addr(sp), _addr(rp),
                                                            _addr(status), _addr(rec)),
                   "fecgpu_rlc_decode_rows_len_host")
+
+    def xor_encode_rows(self, src_rows, src_len, rep_rows, blk_len, nblocks, k, L):
+        """fecgpu_xor_encode_rows_host: host tables and lengths; the rows must be device-accessible."""
+        self._chk(self.lib.fecgpu_xor_encode_rows_host(self.ctx, _addr(src_rows), _addr(src_len), _addr(rep_rows),
+                                                       _addr(blk_len), nblocks, k, L), "fecgpu_xor_encode_rows_host")
+
+    def xor_decode_rows(self, src_rows, src_len, rep_rows, blk_len, sp, rp, status, rec, nblocks, k, L):
+        """fecgpu_xor_decode_rows_host: host tables, lengths, masks, status and recovered."""
+        self._chk(self.lib.fecgpu_xor_decode_rows_host(self.ctx, _addr(src_rows), _addr(src_len), _addr(rep_rows),
+                                                       _addr(blk_len), nblocks, k, L, _addr(sp), _addr(rp),
+                                                       _addr(status), _addr(rec)), "fecgpu_xor_decode_rows_host")

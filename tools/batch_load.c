@@ -290,6 +290,11 @@ static uint16_t ragged_len(int c, long q, int j, int k, int L) {
     return (uint16_t)(lo + u % (mid - lo + 1));
 }
 
+/* XOR legs (bl_run / bl_run_recover): on != 0, the blocks go through the XOR scheme -- the caller passes r = 1,
+ * and e = 1 for recover; the receiver's pool then carries each block's XOR repair.  Default 0: every leg is RLC. */
+static int g_xor;
+void bl_set_xor(int on) { g_xor = on != 0; }
+
 /* batches in flight per sender (1..16; default 4): the back-pressure that bounds queueing latency */
 void bl_set_inflight(int batches) { g_inflight = batches < 1 ? 1 : batches > 16 ? 16 : batches; }
 
@@ -455,6 +460,8 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
                        !sched_setaffinity(0, sizeof near, &near);
     const int ragged = g_ragged_max > 0;
     if (ragged && g_ragged_max < L) return sender_fail(waits);
+    const int xs = g_xor;
+    if (xs && (r != 1 || recover_e > 1)) return sender_fail(waits);
     pquic_fec_batch_cfg_t cfg = {device, batch_blocks, max_delay_us, (uint32_t)(ragged ? g_ragged_max : L), nstreams,
                                  g_poll_blocks};
     pquic_fec_batcher_t *b = pquic_fec_batcher_create(&cfg);
@@ -512,7 +519,9 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
         if (!hc || !fbn || !rep) return sender_fail(waits);
         for (int c = 0; c < nconn; c++) {
             for (long q = 0; q < ppc; q++) fbn[q] = (uint32_t)(c * ppc + q) & 0xffffffu;
-            if (fecgpu_rlc_encode_host(hc, pool[c], rep, ppc, k, r, L, 0, fbn)) return sender_fail(waits);
+            if (xs ? fecgpu_xor_encode_host(hc, pool[c], rep, ppc, k, L)
+                   : fecgpu_rlc_encode_host(hc, pool[c], rep, ppc, k, r, L, 0, fbn))
+                return sender_fail(waits);
             memcpy(pool[c] + (size_t)ppc * k * L, rep, (size_t)ppc * r * L);
         }
         free(fbn);
@@ -617,8 +626,8 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
             }
             s->busy = 1;
             s->t_submit = stamp_us();
-            const int rc = recover_e ? pquic_fec_batch_recover(b, &cnx[c], &s->fb, 0, s->t_submit, on_recovered, s)
-                                     : pquic_fec_batch_generate(b, &cnx[c], &s->fb, 0, s->t_submit, on_done, s);
+            const int rc = recover_e ? pquic_fec_batch_recover(b, &cnx[c], &s->fb, xs, s->t_submit, on_recovered, s)
+                                     : pquic_fec_batch_generate(b, &cnx[c], &s->fb, xs, s->t_submit, on_done, s);
             if (rc) return sender_fail(waits);
             if (g_detail) t_submit += stamp_us() - s->t_submit;
             if ((blk & 15) == 0) pquic_fec_batch_poll(b, stamp_us());
