@@ -45,6 +45,7 @@
 #endif
 #endif
 #include "../../include/fecgpu.h"
+#include "fecgpu_internal.h"
 
 using namespace fecdev;
 
@@ -3631,9 +3632,6 @@ int fecgpu_debug_stamps(uint64_t out[16]) {  // diagnostic builds: the phase sta
 }
 #endif
 
-void fecgpu_host_registry_stats(uint64_t *hits, uint64_t *misses);  // host_path.hip (library-internal)
-void fecgpu_host_yield_stats(uint64_t *slices, uint64_t *waits);      // host_path.hip (library-internal)
-
 void fecgpu_get_stats(fecgpu_stats_t *out) {
   out->encode_calls = g_stats[0].load();
   out->encode_blocks = g_stats[1].load();
@@ -4586,8 +4584,6 @@ static int svc_run_posted(fecgpu_block_svc_t *v, uint64_t t0) {
     }
   }
 }
-
-int fecgpu_host_device_address(const void *p, size_t bytes, uint64_t *dev);  // host_path.hip
 
 static bool svc_addr(const void *p, size_t n, uint64_t *d) { return fecgpu_host_device_address(p, n, d) == FECGPU_OK; }
 

@@ -4,6 +4,8 @@
 // receive, sender.c:1084 on send).  These entry points move a batch of FEC blocks through
 // the device: per sub-batch, H2D copy -> fecgpu_* kernels -> D2H copy on one of `nstreams`
 // streams, so the copies of one sub-batch overlap the kernels of the next.
+// The table forms (*_rows_host, *_rows_len_host) take rows by device address and copy no payload: their
+// per-block arrays go through stage_tables() / unstage_tables(), their launches through for_slices().
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -17,6 +19,7 @@
 #include <vector>
 
 #include "../../include/fecgpu.h"
+#include "fecgpu_internal.h"
 
 namespace {
 constexpr int kMaxStreams = 4;
@@ -118,7 +121,7 @@ bool pinned_remove(uintptr_t base, bool *registered) {
 }
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) void fecgpu_host_registry_stats(uint64_t *hits, uint64_t *misses) {
+extern "C" void fecgpu_host_registry_stats(uint64_t *hits, uint64_t *misses) {
   *hits = g_pin_hits.load();
   *misses = g_pin_misses.load();
 }
@@ -163,12 +166,6 @@ static uint8_t *mapped_host(const void *p, size_t len) {
 // Page-locked host buffers are read (and written) by the kernels directly over PCIe instead of
 // being staged by copies: measured 49.2 -> 51.0 GiB/s encode, 39.2 -> 50.3 GiB/s decode
 // (k16 r4, 2^18 blocks).  Knob zc_read = 0 restores the staged copies (A/B).
-int fecgpu_knob_zc_read(void);  // fec_engine.hip (library-internal, C linkage)
-int fecgpu_rlc_decode_to_internal(const void *src, const void *rep, void *dst, uint64_t nblocks, uint32_t k,
-                                  uint32_t r, uint32_t L, uint32_t fbn_base, const uint32_t *fbn,
-                                  const uint32_t *seeds, const uint64_t *sp, const uint64_t *rp, uint8_t *status,
-                                  uint64_t *recovered, void *ws, size_t wsb, void *stream, int full);  // fec_engine.hip
-int fecgpu_knob_window_sc(void);  // fec_engine.hip (library-internal)
 static bool zc_read() { return fecgpu_knob_zc_read() != 0; }
 
 // ---- zero-copy bulk calls yield to the synchronous hooks ----
@@ -180,14 +177,10 @@ static bool zc_read() { return fecgpu_knob_zc_read() != 0; }
 // while the block service is in use (a hook request within the last yield_window_ms, 100 ms), a zero-copy launch
 // is cut into slices of about yield_slice_kb of payload, alternating over yield_streams of the context's
 // streams (consecutive slices overlap, so the cut costs less), at most yield_depth in flight (knobs;
-// defaults and their measurement in fec_engine.hip knobs_default).  Optionally (yield_gate_us) no
+// defaults and their measurement in fec_engine.hip's FEC_KNOBS table).  Optionally (yield_gate_us) no
 // slice starts while a hook request is pending.  Without hooks nothing changes (one launch).  The
 // hooks still wait for the slices running when they arrive; the slice size trades their p99 against
 // the bulk call's time (about 55-80 us of PCIe transfer per 2.25-2.5 MiB slice).
-int fecgpu_svc_hooks_pending(void);                                  // fec_engine.hip (library-internal)
-uint64_t fecgpu_svc_last_request_us(void);                           // fec_engine.hip (library-internal)
-void fecgpu_knob_yield(int *slice_kb, int *depth, int *gate_us, int *streams, int *always,
-                       int *window_ms);  // fec_engine.hip
 namespace {
 std::atomic<uint64_t> g_yield_slices{0}, g_yield_waits{0};
 
@@ -240,7 +233,7 @@ struct Pacer {
 };
 }  // namespace
 
-__attribute__((visibility("hidden"))) void fecgpu_host_yield_stats(uint64_t *slices, uint64_t *waits) {
+void fecgpu_host_yield_stats(uint64_t *slices, uint64_t *waits) {
   *slices = g_yield_slices.load();
   *waits = g_yield_waits.load();
 }
@@ -269,6 +262,82 @@ static int finish(fecgpu_host_ctx_t *c, int rc) {
     rc = FECGPU_ERR_HIP;                      \
     break;                                    \
   }
+
+// ---- the per-block arrays of the table forms (the *_rows_host, *_rows_len_host entry points) ----
+// One array of a call: `bpb` bytes per block at `host`; 0 bytes: an array without entries (the repair
+// table, repair lengths and seeds at r == 0, fbn[] not given), never looked up, copied or read.
+extern "C++" {
+namespace {
+struct Table {
+  void *host;
+  size_t bpb;
+  bool out;                // written by the kernels: copied back when the arrays were staged
+  uint8_t *dev = nullptr;  // where the kernels find it (stage_tables)
+  template <class T> T *at(uint64_t b0) const { return (T *)(dev + b0 * bpb); }  // block b0's entries
+};
+Table in(const void *p, size_t bpb) { return Table{const_cast<void *>(p), bpb, false}; }
+Table out(void *p, size_t bpb) { return Table{p, bpb, true}; }
+inline size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
+}  // namespace
+
+// Device addresses for a call's arrays, all or nothing.  The arrays are looked up in the order given, up
+// to the first that is not page-locked (a miss costs a query of the runtime): all page-locked (the
+// batching adapter's job tables) and the kernels use them in place; else each gets its part of slot 0's
+// d_aux, from a 16-byte boundary, and the inputs are copied there on slot 0's stream.  An array without
+// entries takes the first array's address as a stand-in.
+template <size_t N>
+static int stage_tables(fecgpu_host_ctx_t *c, Table (&t)[N], uint64_t nblocks, bool *in_place) {
+  *in_place = true;
+  for (size_t i = 0; i < N && *in_place; i++)
+    if (t[i].bpb) *in_place = (t[i].dev = mapped_host(t[i].host, nblocks * t[i].bpb)) != nullptr;
+  if (!*in_place) {
+    Slot &s = c->slot[0];
+    size_t need = 0;
+    for (const Table &x : t) need += pad16(nblocks * x.bpb);
+    HCHK(grow(&s.d_aux, &s.cap_aux, need));
+    uint8_t *a = (uint8_t *)s.d_aux;
+    for (Table &x : t) {
+      x.dev = a;
+      a += pad16(nblocks * x.bpb);
+      if (x.bpb && !x.out) HCHK(hipMemcpyAsync(x.dev, x.host, nblocks * x.bpb, hipMemcpyHostToDevice, s.st));
+    }
+  }
+  for (Table &x : t)
+    if (!x.bpb) x.dev = t[0].dev;
+  return FECGPU_OK;
+}
+
+// after the launches: the outputs of staged arrays back into the caller's, unless the call failed
+template <size_t N>
+static int unstage_tables(fecgpu_host_ctx_t *c, const Table (&t)[N], uint64_t nblocks, bool in_place, int rc) {
+  if (rc != FECGPU_OK || in_place) return rc;
+  for (const Table &x : t)
+    if (x.out) HCHK(hipMemcpyAsync(x.host, x.dev, nblocks * x.bpb, hipMemcpyDeviceToHost, c->slot[0].st));
+  return FECGPU_OK;
+}
+
+// The loop of the table forms.  Arrays in place and the hooks in use: the Pacer's slices, alternating over
+// its streams.  Otherwise steps of `whole` blocks, the entry point's own unsliced step: round-robin over
+// the context's streams with the arrays in place, all on slot 0 when they were copied (its stream carries
+// the copies).  launch(b0, m, slot) grows what the form needs of the slot's buffers and makes the one launch
+// for blocks [b0, b0 + m) on the slot's stream; m never grows during a call, so a slot's buffers are not
+// reallocated under a launch still running.  An error ends the loop, not the call: finish() drains.
+template <class Launch>
+static int for_slices(fecgpu_host_ctx_t *c, uint64_t nblocks, size_t block_bytes, uint64_t whole, bool in_place,
+                      Launch &&launch) {
+  Pacer pc(c, nblocks, block_bytes);
+  if (!in_place) pc.slice = 0;
+  const uint64_t step = pc.slice ? pc.slice : whole;
+  int si = 0, rc = FECGPU_OK;
+  for (uint64_t b0 = 0; b0 < nblocks; b0 += step) {
+    LCHK(pc.before());
+    if ((rc = launch(b0, std::min(step, nblocks - b0), c->slot[pc.slice ? pc.n % pc.streams : si]))) break;
+    LCHK(pc.after());
+    if (in_place) si = (si + 1) % c->ns;
+  }
+  return rc;
+}
+}  // extern "C++"
 
 int fecgpu_rlc_encode_host(fecgpu_host_ctx_t *c, const void *src, void *rep, uint64_t nblocks, uint32_t k,
                            uint32_t r, uint32_t L, uint32_t fbn_base, const uint32_t *fbn) {
@@ -333,35 +402,17 @@ int fecgpu_rlc_encode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, 
   if (!nblocks || !r) return FECGPU_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HCHK(hipSetDevice(c->device));
-  Slot &s = c->slot[0];
-  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
-  const uint64_t *dr = (const uint64_t *)mapped_host(rep_rows, nblocks * r * 8);
-  const uint32_t *df = fbn ? (const uint32_t *)mapped_host(fbn, nblocks * 4) : nullptr;
-  int rc = FECGPU_OK;
-  do {
-    if (!ds || !dr || (fbn && !df)) {  // pageable tables: one device copy
-      const size_t need = nblocks * (k + r) * 8 + (fbn ? nblocks * 4 : 0);
-      LCHK(grow(&s.d_aux, &s.cap_aux, need));
-      uint8_t *a = (uint8_t *)s.d_aux;
-      LCHK(hipMemcpyAsync(a, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync(a + nblocks * k * 8, rep_rows, nblocks * r * 8, hipMemcpyHostToDevice, s.st));
-      if (fbn) LCHK(hipMemcpyAsync(a + nblocks * (k + r) * 8, fbn, nblocks * 4, hipMemcpyHostToDevice, s.st));
-      ds = (const uint64_t *)a;
-      dr = (const uint64_t *)(a + nblocks * k * 8);
-      df = fbn ? (const uint32_t *)(a + nblocks * (k + r) * 8) : nullptr;
-    }
-    Pacer pc(c, nblocks, (size_t)(k + r) * L);  // hooks in use: slices that yield to them
-    if (pc.slice && pc.streams > 1) LCHK(hipStreamSynchronize(s.st));  // copied tables, read from other streams
-    for (uint64_t b0 = 0, step = pc.slice ? pc.slice : nblocks; b0 < nblocks; b0 += step) {
-      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
-      LCHK(pc.before());
+  enum { SRC, REP, FBN };
+  Table t[] = {in(src_rows, (size_t)k * 8), in(rep_rows, (size_t)r * 8), in(fbn, fbn ? 4 : 0)};
+  bool in_place;
+  int rc = stage_tables(c, t, nblocks, &in_place);
+  if (!rc)  // unsliced: the whole batch in one launch
+    rc = for_slices(c, nblocks, (size_t)(k + r) * L, nblocks, in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
       // without fbn[] block b is block number b (fecgpu.h:21): slice b0 starts at b0, not 0
-      if ((rc = fecgpu_rlc_encode_rows(ds + b0 * k, dr + b0 * r, m, k, r, L, df ? 0u : (uint32_t)(b0 & 0xffffffu),
-                                       df ? df + b0 : nullptr, pc.stream(s.st))))
-        break;
-      LCHK(pc.after());
-    }
-  } while (0);
+      return fecgpu_rlc_encode_rows(t[SRC].at<const uint64_t>(b0), t[REP].at<const uint64_t>(b0), m, k, r, L,
+                                    fbn ? 0u : (uint32_t)(b0 & 0xffffffu),
+                                    fbn ? t[FBN].at<const uint32_t>(b0) : nullptr, w.st);
+    });
   return finish(c, rc);
 }
 
@@ -555,74 +606,25 @@ int fecgpu_rlc_decode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, 
   if (!nblocks) return FECGPU_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HCHK(hipSetDevice(c->device));
-  Slot &s = c->slot[0];
-  const uint32_t nseed = r ? r : 1;
-  // every array page-locked (the batching adapter's job tables): the kernels use them in place.  With
-  // r == 0 the repair table and seeds have no entries and are never read: the source table stands in
-  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
-  const uint64_t *dr = !ds ? nullptr : r ? (const uint64_t *)mapped_host(rep_rows, nblocks * r * 8) : ds;
-  const uint32_t *dseed = !dr ? nullptr : r ? (const uint32_t *)mapped_host(seeds, nblocks * r * 4)
-                                            : (const uint32_t *)ds;
-  const uint64_t *dsp = dseed ? (const uint64_t *)mapped_host(sp, nblocks * 16) : nullptr;
-  const uint64_t *drp = dsp ? (const uint64_t *)mapped_host(rp, nblocks * 16) : nullptr;
-  uint8_t *dst = drp ? mapped_host(status, nblocks) : nullptr;
-  uint64_t *drec = dst ? (uint64_t *)mapped_host(recovered, nblocks * 16) : nullptr;
-  int rc = FECGPU_OK;
-  do {
-    const size_t wsb = fecgpu_rlc_decode_workspace(nblocks, k, r);
-    LCHK(grow(&s.d_ws, &s.cap_ws, wsb));
-    if (!drec) {  // pageable: one device copy of the tables and masks, status and masks copied back
-      const size_t tb = nblocks * (k + nseed) * 8, sdb = (nblocks * nseed * 4 + 15) & ~(size_t)15;
-      LCHK(grow(&s.d_aux, &s.cap_aux, tb + sdb + nblocks * 48 + nblocks));
-      uint8_t *a = (uint8_t *)s.d_aux;
-      ds = (const uint64_t *)a;
-      dr = (const uint64_t *)(a + nblocks * k * 8);
-      dseed = (const uint32_t *)(a + tb);
-      uint64_t *m = (uint64_t *)(a + tb + sdb);
-      dsp = m;
-      drp = m + 2 * nblocks;
-      drec = m + 4 * nblocks;
-      dst = (uint8_t *)(m + 6 * nblocks);
-      LCHK(hipMemcpyAsync((void *)ds, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
-      if (r) LCHK(hipMemcpyAsync((void *)dr, rep_rows, nblocks * r * 8, hipMemcpyHostToDevice, s.st));
-      if (r) LCHK(hipMemcpyAsync((void *)dseed, seeds, nblocks * r * 4, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)dsp, sp, nblocks * 16, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)drp, rp, nblocks * 16, hipMemcpyHostToDevice, s.st));
-      if ((rc = fecgpu_rlc_decode_rows(ds, dr, nblocks, k, r, L, dseed, dsp, drp, dst, drec, s.d_ws, s.cap_ws, s.st)))
-        break;
-      LCHK(hipMemcpyAsync(status, dst, nblocks, hipMemcpyDeviceToHost, s.st));
-      LCHK(hipMemcpyAsync(recovered, drec, nblocks * 16, hipMemcpyDeviceToHost, s.st));
-      break;
-    }
-    Pacer pc(c, nblocks, (size_t)(k + r) * L);  // hooks in use: slices that yield to them
-    for (uint64_t b0 = 0, step = pc.slice ? pc.slice : nblocks; b0 < nblocks; b0 += step) {
-      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
-      LCHK(pc.before());
-      // one workspace per stream the slices alternate over
-      Slot &ws = c->slot[pc.slice ? pc.n % pc.streams : 0];
-      if (&ws != &s) LCHK(grow(&ws.d_ws, &ws.cap_ws, fecgpu_rlc_decode_workspace(m, k, r)));
-      if ((rc = fecgpu_rlc_decode_rows(ds + b0 * k, dr + b0 * nseed, m, k, r, L, dseed + b0 * nseed, dsp + 2 * b0,
-                                       drp + 2 * b0, dst + b0, drec + 2 * b0, ws.d_ws, ws.cap_ws, pc.stream(s.st))))
-        break;
-      LCHK(pc.after());
-    }
-  } while (0);
-  return finish(c, rc);
+  enum { SRC, REP, SEED, SP, RP, ST, REC };
+  Table t[] = {in(src_rows, (size_t)k * 8), in(rep_rows, (size_t)r * 8), in(seeds, (size_t)r * 4), in(sp, 16),
+               in(rp, 16),                  out(status, 1),              out(recovered, 16)};
+  bool in_place;
+  int rc = stage_tables(c, t, nblocks, &in_place);
+  if (!rc)  // unsliced: the whole batch in one launch
+    rc = for_slices(c, nblocks, (size_t)(k + r) * L, nblocks, in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
+      HCHK(grow(&w.d_ws, &w.cap_ws, fecgpu_rlc_decode_workspace(m, k, r)));  // one workspace per stream
+      return fecgpu_rlc_decode_rows(t[SRC].at<const uint64_t>(b0), t[REP].at<const uint64_t>(b0), m, k, r, L,
+                                    t[SEED].at<const uint32_t>(b0), t[SP].at<const uint64_t>(b0),
+                                    t[RP].at<const uint64_t>(b0), t[ST].at<uint8_t>(b0), t[REC].at<uint64_t>(b0),
+                                    w.d_ws, w.cap_ws, w.st);
+    });
+  return finish(c, unstage_tables(c, t, nblocks, in_place, rc));
 }
 
 // ---- ragged rows (fecgpu_rlc_encode_rows_len_host / fecgpu_rlc_decode_rows_len_host) ----
-// fec_engine.hip (library-internal): the device forms with the packed arrays given one by one, so a
-// sub-batch packs into its slot's d_src / d_rep and plans in its d_ws
-int fecgpu_rlc_encode_rows_len_internal(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
-                                        const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L,
-                                        uint32_t fbn_base, const uint32_t *fbn, void *psrc, void *prep, void *stream);
-int fecgpu_rlc_decode_rows_len_internal(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
-                                        const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
-                                        uint32_t r, uint32_t L, const uint32_t *rep_seed, const uint64_t *sp,
-                                        const uint64_t *rp, uint8_t *status, uint64_t *recovered, void *psrc,
-                                        void *prep, void *prec, void *ws, size_t wsb, void *stream);
-int fecgpu_set_error_internal(int code, const char *what);
-
+// The *_rows_len_internal forms take the packed arrays one by one, so a sub-batch packs into its slot's
+// d_src / d_rep and plans in its d_ws.
 static int rows_len_invalid(const char *what) { return fecgpu_set_error_internal(FECGPU_ERR_INVALID, what); }
 
 // check_common's shape rules (the tables are checked by the callers)
@@ -658,50 +660,21 @@ int fecgpu_rlc_encode_rows_len_host(fecgpu_host_ctx_t *c, const uint64_t *src_ro
   if (!nblocks || !r) return FECGPU_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HCHK(hipSetDevice(c->device));
-  Slot &s = c->slot[0];
-  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
-  const uint64_t *dr = ds ? (const uint64_t *)mapped_host(rep_rows, nblocks * r * 8) : nullptr;
-  const uint32_t *dsl = dr ? (const uint32_t *)mapped_host(src_len, nblocks * k * 4) : nullptr;
-  const uint32_t *dbl = dsl ? (const uint32_t *)mapped_host(blk_len, nblocks * 4) : nullptr;
-  const uint32_t *df = dbl && fbn ? (const uint32_t *)mapped_host(fbn, nblocks * 4) : nullptr;
-  const bool in_place = dbl && (!fbn || df);
-  int rc = FECGPU_OK;
-  do {
-    if (!in_place) {  // pageable tables: one device copy, and the whole batch on this slot's stream
-      const size_t o_rep = nblocks * k * 8, o_sl = o_rep + nblocks * r * 8, o_bl = o_sl + nblocks * k * 4,
-                   o_fbn = o_bl + nblocks * 4;
-      LCHK(grow(&s.d_aux, &s.cap_aux, o_fbn + (fbn ? nblocks * 4 : 0)));
-      uint8_t *a = (uint8_t *)s.d_aux;
-      LCHK(hipMemcpyAsync(a, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync(a + o_rep, rep_rows, nblocks * r * 8, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync(a + o_sl, src_len, nblocks * k * 4, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync(a + o_bl, blk_len, nblocks * 4, hipMemcpyHostToDevice, s.st));
-      if (fbn) LCHK(hipMemcpyAsync(a + o_fbn, fbn, nblocks * 4, hipMemcpyHostToDevice, s.st));
-      ds = (const uint64_t *)a;
-      dr = (const uint64_t *)(a + o_rep);
-      dsl = (const uint32_t *)(a + o_sl);
-      dbl = (const uint32_t *)(a + o_bl);
-      df = fbn ? (const uint32_t *)(a + o_fbn) : nullptr;
-    }
-    Pacer pc(c, nblocks, (size_t)(k + r) * L);  // hooks in use: slices that yield to them
-    if (!in_place) pc.slice = 0;
-    const uint64_t step = pc.slice ? pc.slice : sub_batch(c, nblocks, (size_t)(k + r) * L);
-    int si = 0;
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += step) {
-      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
-      LCHK(pc.before());
-      Slot &w = c->slot[pc.slice ? pc.n % pc.streams : si];  // the packed rows of a sub-batch: its slot's buffers
-      LCHK(grow(&w.d_src, &w.cap_src, step * k * L));
-      LCHK(grow(&w.d_rep, &w.cap_rep, step * r * L));
+  enum { SRC, REP, SLEN, BLEN, FBN };
+  Table t[] = {in(src_rows, k * 8), in(rep_rows, r * 8), in(src_len, k * 4), in(blk_len, 4), in(fbn, fbn ? 4 : 0)};
+  bool in_place;
+  int rc = stage_tables(c, t, nblocks, &in_place);
+  const size_t bb = (size_t)(k + r) * L;
+  if (!rc)
+    rc = for_slices(c, nblocks, bb, sub_batch(c, nblocks, bb), in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
+      HCHK(grow(&w.d_src, &w.cap_src, m * k * L));  // the packed rows of a sub-batch: its slot's buffers
+      HCHK(grow(&w.d_rep, &w.cap_rep, m * r * L));
       // without fbn[] block b is block number b (fecgpu.h:21): sub-batch b0 starts at b0, not 0
-      if ((rc = fecgpu_rlc_encode_rows_len_internal(ds + b0 * k, dsl + b0 * k, dr + b0 * r, dbl + b0, m, k, r, L,
-                                                    df ? 0u : (uint32_t)(b0 & 0xffffffu), df ? df + b0 : nullptr,
-                                                    w.d_src, w.d_rep, w.st)))
-        break;
-      LCHK(pc.after());
-      if (in_place) si = (si + 1) % c->ns;
-    }
-  } while (0);
+      return fecgpu_rlc_encode_rows_len_internal(
+          t[SRC].at<const uint64_t>(b0), t[SLEN].at<const uint32_t>(b0), t[REP].at<const uint64_t>(b0),
+          t[BLEN].at<const uint32_t>(b0), m, k, r, L, fbn ? 0u : (uint32_t)(b0 & 0xffffffu),
+          fbn ? t[FBN].at<const uint32_t>(b0) : nullptr, w.d_src, w.d_rep, w.st);
+    });
   return finish(c, rc);
 }
 
@@ -718,77 +691,27 @@ int fecgpu_rlc_decode_rows_len_host(fecgpu_host_ctx_t *c, const uint64_t *src_ro
   if (!nblocks) return FECGPU_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HCHK(hipSetDevice(c->device));
-  Slot &s = c->slot[0];
-  const uint32_t nseed = r ? r : 1, em = k < r ? k : r;
-  // every array page-locked (the batching adapter's job tables): the kernels use them in place.  With
-  // r == 0 the repair tables and seeds have no entries and are never read: the source tables stand in
-  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
-  const uint32_t *dsl = ds ? (const uint32_t *)mapped_host(src_len, nblocks * k * 4) : nullptr;
-  const uint32_t *dbl = dsl ? (const uint32_t *)mapped_host(blk_len, nblocks * 4) : nullptr;
-  const uint64_t *dr = !dbl ? nullptr : r ? (const uint64_t *)mapped_host(rep_rows, nblocks * r * 8) : ds;
-  const uint32_t *drl = !dr ? nullptr : r ? (const uint32_t *)mapped_host(rep_len, nblocks * r * 4) : dsl;
-  const uint32_t *dseed = !drl ? nullptr : r ? (const uint32_t *)mapped_host(seeds, nblocks * r * 4) : dsl;
-  const uint64_t *dsp = dseed ? (const uint64_t *)mapped_host(sp, nblocks * 16) : nullptr;
-  const uint64_t *drp = dsp ? (const uint64_t *)mapped_host(rp, nblocks * 16) : nullptr;
-  uint8_t *dst = drp ? mapped_host(status, nblocks) : nullptr;
-  uint64_t *drec = dst ? (uint64_t *)mapped_host(recovered, nblocks * 16) : nullptr;
-  const bool in_place = drec != nullptr;
-  int rc = FECGPU_OK;
-  do {
-    if (!in_place) {  // pageable: one device copy of the tables and masks, the whole batch on this slot's stream
-      const size_t o_rep = nblocks * k * 8, o_m = o_rep + nblocks * nseed * 8, o_sl = o_m + nblocks * 48,
-                   o_rl = o_sl + nblocks * k * 4, o_bl = o_rl + nblocks * nseed * 4, o_seed = o_bl + nblocks * 4,
-                   o_st = o_seed + nblocks * nseed * 4;
-      LCHK(grow(&s.d_aux, &s.cap_aux, o_st + nblocks));
-      uint8_t *a = (uint8_t *)s.d_aux;
-      ds = (const uint64_t *)a;
-      dr = (const uint64_t *)(a + o_rep);
-      uint64_t *mk = (uint64_t *)(a + o_m);
-      dsp = mk;
-      drp = mk + 2 * nblocks;
-      drec = mk + 4 * nblocks;
-      dsl = (const uint32_t *)(a + o_sl);
-      drl = (const uint32_t *)(a + o_rl);
-      dbl = (const uint32_t *)(a + o_bl);
-      dseed = (const uint32_t *)(a + o_seed);
-      dst = a + o_st;
-      LCHK(hipMemcpyAsync((void *)ds, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)dsl, src_len, nblocks * k * 4, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)dbl, blk_len, nblocks * 4, hipMemcpyHostToDevice, s.st));
-      if (r) {
-        LCHK(hipMemcpyAsync((void *)dr, rep_rows, nblocks * r * 8, hipMemcpyHostToDevice, s.st));
-        LCHK(hipMemcpyAsync((void *)drl, rep_len, nblocks * r * 4, hipMemcpyHostToDevice, s.st));
-        LCHK(hipMemcpyAsync((void *)dseed, seeds, nblocks * r * 4, hipMemcpyHostToDevice, s.st));
-      }
-      LCHK(hipMemcpyAsync((void *)dsp, sp, nblocks * 16, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)drp, rp, nblocks * 16, hipMemcpyHostToDevice, s.st));
-    }
-    Pacer pc(c, nblocks, (size_t)(k + r) * L);  // hooks in use: slices that yield to them
-    if (!in_place) pc.slice = 0;
-    const uint64_t step = pc.slice ? pc.slice : sub_batch(c, nblocks, (size_t)(k + r) * L);
-    const size_t o_rec = pad256(step * r * L);
-    int si = 0;
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += step) {
-      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
-      LCHK(pc.before());
-      Slot &w = c->slot[pc.slice ? pc.n % pc.streams : si];  // packed sources in d_src, repairs and recovered rows in d_rep
-      LCHK(grow(&w.d_src, &w.cap_src, step * k * L));
-      LCHK(grow(&w.d_rep, &w.cap_rep, o_rec + pad256(step * em * L) + 256));
-      LCHK(grow(&w.d_ws, &w.cap_ws, fecgpu_rlc_decode_workspace(step, k, r)));
-      if ((rc = fecgpu_rlc_decode_rows_len_internal(ds + b0 * k, dsl + b0 * k, dr + b0 * nseed, drl + b0 * nseed,
-                                                    dbl + b0, m, k, r, L, dseed + b0 * nseed, dsp + 2 * b0,
-                                                    drp + 2 * b0, dst + b0, drec + 2 * b0, w.d_src, w.d_rep,
-                                                    (uint8_t *)w.d_rep + o_rec, w.d_ws, w.cap_ws, w.st)))
-        break;
-      LCHK(pc.after());
-      if (in_place) si = (si + 1) % c->ns;
-    }
-    if (rc == FECGPU_OK && !in_place) {
-      LCHK(hipMemcpyAsync(status, dst, nblocks, hipMemcpyDeviceToHost, s.st));
-      LCHK(hipMemcpyAsync(recovered, drec, nblocks * 16, hipMemcpyDeviceToHost, s.st));
-    }
-  } while (0);
-  return finish(c, rc);
+  const uint32_t em = k < r ? k : r;
+  enum { SRC, SLEN, BLEN, REP, RLEN, SEED, SP, RP, ST, REC };
+  Table t[] = {in(src_rows, k * 8), in(src_len, k * 4), in(blk_len, 4), in(rep_rows, r * 8), in(rep_len, r * 4),
+               in(seeds, r * 4),    in(sp, 16),         in(rp, 16),     out(status, 1),      out(recovered, 16)};
+  bool in_place;
+  int rc = stage_tables(c, t, nblocks, &in_place);
+  const size_t bb = (size_t)(k + r) * L;
+  if (!rc)
+    rc = for_slices(c, nblocks, bb, sub_batch(c, nblocks, bb), in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
+      // packed sources in d_src; d_rep holds the packed repairs at 0 and the recovered rows behind them
+      const size_t o_rec = pad256(m * r * L);
+      HCHK(grow(&w.d_src, &w.cap_src, m * k * L));
+      HCHK(grow(&w.d_rep, &w.cap_rep, o_rec + pad256(m * em * L) + 256));
+      HCHK(grow(&w.d_ws, &w.cap_ws, fecgpu_rlc_decode_workspace(m, k, r)));
+      return fecgpu_rlc_decode_rows_len_internal(
+          t[SRC].at<const uint64_t>(b0), t[SLEN].at<const uint32_t>(b0), t[REP].at<const uint64_t>(b0),
+          t[RLEN].at<const uint32_t>(b0), t[BLEN].at<const uint32_t>(b0), m, k, r, L, t[SEED].at<const uint32_t>(b0),
+          t[SP].at<const uint64_t>(b0), t[RP].at<const uint64_t>(b0), t[ST].at<uint8_t>(b0), t[REC].at<uint64_t>(b0),
+          w.d_src, w.d_rep, (uint8_t *)w.d_rep + o_rec, w.d_ws, w.cap_ws, w.st);
+    });
+  return finish(c, unstage_tables(c, t, nblocks, in_place, rc));
 }
 
 // ---- XOR on rows (fecgpu_xor_encode_rows_host / fecgpu_xor_decode_rows_host) ----
@@ -803,40 +726,16 @@ int fecgpu_xor_encode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, 
   if (!nblocks) return FECGPU_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HCHK(hipSetDevice(c->device));
-  Slot &s = c->slot[0];
-  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
-  const uint64_t *dr = ds ? (const uint64_t *)mapped_host(rep_rows, nblocks * 8) : nullptr;
-  const uint32_t *dsl = dr ? (const uint32_t *)mapped_host(src_len, nblocks * k * 4) : nullptr;
-  const uint32_t *dbl = dsl ? (const uint32_t *)mapped_host(blk_len, nblocks * 4) : nullptr;
-  const bool in_place = dbl != nullptr;
-  int rc = FECGPU_OK;
-  do {
-    if (!in_place) {  // pageable tables: one device copy, and the whole batch on this slot's stream
-      const size_t o_rep = nblocks * k * 8, o_sl = o_rep + nblocks * 8, o_bl = o_sl + nblocks * k * 4;
-      LCHK(grow(&s.d_aux, &s.cap_aux, o_bl + nblocks * 4));
-      uint8_t *a = (uint8_t *)s.d_aux;
-      LCHK(hipMemcpyAsync(a, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync(a + o_rep, rep_rows, nblocks * 8, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync(a + o_sl, src_len, nblocks * k * 4, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync(a + o_bl, blk_len, nblocks * 4, hipMemcpyHostToDevice, s.st));
-      ds = (const uint64_t *)a;
-      dr = (const uint64_t *)(a + o_rep);
-      dsl = (const uint32_t *)(a + o_sl);
-      dbl = (const uint32_t *)(a + o_bl);
-    }
-    Pacer pc(c, nblocks, (size_t)(k + 1) * L);  // hooks in use: slices that yield to them
-    if (!in_place) pc.slice = 0;
-    const uint64_t step = pc.slice ? pc.slice : sub_batch(c, nblocks, (size_t)(k + 1) * L);
-    int si = 0;
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += step) {
-      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
-      LCHK(pc.before());
-      Slot &w = c->slot[pc.slice ? pc.n % pc.streams : si];
-      if ((rc = fecgpu_xor_encode_rows(ds + b0 * k, dsl + b0 * k, dr + b0, dbl + b0, m, k, L, w.st))) break;
-      LCHK(pc.after());
-      if (in_place) si = (si + 1) % c->ns;
-    }
-  } while (0);
+  enum { SRC, REP, SLEN, BLEN };
+  Table t[] = {in(src_rows, k * 8), in(rep_rows, 8), in(src_len, k * 4), in(blk_len, 4)};
+  bool in_place;
+  int rc = stage_tables(c, t, nblocks, &in_place);
+  const size_t bb = (size_t)(k + 1) * L;
+  if (!rc)
+    rc = for_slices(c, nblocks, bb, sub_batch(c, nblocks, bb), in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
+      return fecgpu_xor_encode_rows(t[SRC].at<const uint64_t>(b0), t[SLEN].at<const uint32_t>(b0),
+                                    t[REP].at<const uint64_t>(b0), t[BLEN].at<const uint32_t>(b0), m, k, L, w.st);
+    });
   return finish(c, rc);
 }
 
@@ -852,59 +751,20 @@ int fecgpu_xor_decode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, 
   if (!nblocks) return FECGPU_OK;
   std::lock_guard<std::mutex> g(c->mu);
   HCHK(hipSetDevice(c->device));
-  Slot &s = c->slot[0];
-  const uint64_t *ds = (const uint64_t *)mapped_host(src_rows, nblocks * k * 8);
-  const uint32_t *dsl = ds ? (const uint32_t *)mapped_host(src_len, nblocks * k * 4) : nullptr;
-  const uint32_t *dbl = dsl ? (const uint32_t *)mapped_host(blk_len, nblocks * 4) : nullptr;
-  const uint64_t *dr = dbl ? (const uint64_t *)mapped_host(rep_rows, nblocks * 8) : nullptr;
-  const uint64_t *dsp = dr ? (const uint64_t *)mapped_host(sp, nblocks * 16) : nullptr;
-  const uint64_t *drp = dsp ? (const uint64_t *)mapped_host(rp, nblocks * 16) : nullptr;
-  uint8_t *dst = drp ? mapped_host(status, nblocks) : nullptr;
-  uint64_t *drec = dst ? (uint64_t *)mapped_host(recovered, nblocks * 16) : nullptr;
-  const bool in_place = drec != nullptr;
-  int rc = FECGPU_OK;
-  do {
-    if (!in_place) {  // pageable: one device copy of the tables and masks, the whole batch on this slot's stream
-      const size_t o_rep = nblocks * k * 8, o_m = o_rep + nblocks * 8, o_sl = o_m + nblocks * 48,
-                   o_bl = o_sl + nblocks * k * 4, o_st = o_bl + nblocks * 4;
-      LCHK(grow(&s.d_aux, &s.cap_aux, o_st + nblocks));
-      uint8_t *a = (uint8_t *)s.d_aux;
-      ds = (const uint64_t *)a;
-      dr = (const uint64_t *)(a + o_rep);
-      uint64_t *mk = (uint64_t *)(a + o_m);
-      dsp = mk;
-      drp = mk + 2 * nblocks;
-      drec = mk + 4 * nblocks;
-      dsl = (const uint32_t *)(a + o_sl);
-      dbl = (const uint32_t *)(a + o_bl);
-      dst = a + o_st;
-      LCHK(hipMemcpyAsync((void *)ds, src_rows, nblocks * k * 8, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)dr, rep_rows, nblocks * 8, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)dsl, src_len, nblocks * k * 4, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)dbl, blk_len, nblocks * 4, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)dsp, sp, nblocks * 16, hipMemcpyHostToDevice, s.st));
-      LCHK(hipMemcpyAsync((void *)drp, rp, nblocks * 16, hipMemcpyHostToDevice, s.st));
-    }
-    Pacer pc(c, nblocks, (size_t)(k + 1) * L);  // hooks in use: slices that yield to them
-    if (!in_place) pc.slice = 0;
-    const uint64_t step = pc.slice ? pc.slice : sub_batch(c, nblocks, (size_t)(k + 1) * L);
-    int si = 0;
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += step) {
-      const uint64_t m = nblocks - b0 < step ? nblocks - b0 : step;
-      LCHK(pc.before());
-      Slot &w = c->slot[pc.slice ? pc.n % pc.streams : si];
-      if ((rc = fecgpu_xor_decode_rows(ds + b0 * k, dsl + b0 * k, dr + b0, dbl + b0, m, k, L, dsp + 2 * b0,
-                                       drp + 2 * b0, dst + b0, drec + 2 * b0, w.st)))
-        break;
-      LCHK(pc.after());
-      if (in_place) si = (si + 1) % c->ns;
-    }
-    if (rc == FECGPU_OK && !in_place) {
-      LCHK(hipMemcpyAsync(status, dst, nblocks, hipMemcpyDeviceToHost, s.st));
-      LCHK(hipMemcpyAsync(recovered, drec, nblocks * 16, hipMemcpyDeviceToHost, s.st));
-    }
-  } while (0);
-  return finish(c, rc);
+  enum { SRC, SLEN, BLEN, REP, SP, RP, ST, REC };
+  Table t[] = {in(src_rows, k * 8), in(src_len, k * 4), in(blk_len, 4),      in(rep_rows, 8),
+               in(sp, 16),          in(rp, 16),         out(status, 1),      out(recovered, 16)};
+  bool in_place;
+  int rc = stage_tables(c, t, nblocks, &in_place);
+  const size_t bb = (size_t)(k + 1) * L;
+  if (!rc)
+    rc = for_slices(c, nblocks, bb, sub_batch(c, nblocks, bb), in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
+      return fecgpu_xor_decode_rows(t[SRC].at<const uint64_t>(b0), t[SLEN].at<const uint32_t>(b0),
+                                    t[REP].at<const uint64_t>(b0), t[BLEN].at<const uint32_t>(b0), m, k, L,
+                                    t[SP].at<const uint64_t>(b0), t[RP].at<const uint64_t>(b0), t[ST].at<uint8_t>(b0),
+                                    t[REC].at<uint64_t>(b0), w.st);
+    });
+  return finish(c, unstage_tables(c, t, nblocks, in_place, rc));
 }
 
 int fecgpu_xor_decode_host(fecgpu_host_ctx_t *c, void *src, const void *rep, uint64_t nblocks, uint32_t k,
