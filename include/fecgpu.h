@@ -163,6 +163,32 @@ int fecgpu_rlc_decode_rows_len(const uint64_t *src_rows, const uint32_t *src_len
                                const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
                                uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same on ragged rows in ONE pass over memory: no gather, no packed batch, no scatter.  The data
+ * kernels of fecgpu_rlc_encode_rows / fecgpu_rlc_decode_rows run length-aware bodies that read every
+ * input row through a buffer descriptor bounded by its own length (bytes past it count as zero and are
+ * not read) and store exactly blk_len[b] bytes per output row.  Tables, lengths, clamping (blk_len to
+ * symbol_size, src_len / rep_len to blk_len[b]) and address rules are those of the *_rows_len forms: rows
+ * 4-byte aligned, below 2^48, in device memory or mapped page-locked host memory; a row of 0 bytes and
+ * an absent row are never dereferenced and may have address 0; a load may touch the aligned dword that
+ * holds a row's last byte and nothing after it; stores are 16-B / dword stores and byte stores for the
+ * last 1-3 bytes, no dword is read-modify-written, nothing is written past blk_len[b] bytes of a row.
+ * Encode needs no workspace and writes to every repair row the bytes fecgpu_rlc_encode_rows_len writes.
+ * Decode needs fecgpu_rlc_decode_workspace(nblocks, k, r) only; status[] and recovered[] are exactly what
+ * fecgpu_rlc_decode_seeded gives on the zero-padded rows, and every missing source whose recovered bit is
+ * set holds its blk_len[b] bytes.  As in fecgpu_rlc_decode_rows the data pass writes the unknown rows of a
+ * RECOVERED block before the zero/undetermined rule is known, so -- unlike fecgpu_rlc_decode_rows_len -- a
+ * missing source of a RECOVERED block whose bit stays clear may have received blk_len[b] bytes too (the
+ * reference's unspecified bytes).  Blocks of any other status are neither read nor written.  Both calls
+ * are asynchronous on `stream`, allocate nothing and can be captured into a graph. */
+int fecgpu_rlc_encode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                 const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r,
+                                 uint32_t symbol_size, uint32_t fbn_base, const uint32_t *fbn, void *stream);
+int fecgpu_rlc_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                 const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                 uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                 const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                 uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream);
+
 /* XOR encode (r == 1): rep[b][0] = XOR_j src[b][j]. */
 int fecgpu_xor_encode(const void *src, void *rep, uint64_t nblocks, uint32_t k,
                       uint32_t symbol_size, void *stream);
@@ -358,6 +384,17 @@ int fecgpu_rlc_decode_rows_len_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_
                                     uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
                                     const uint32_t *rep_seed, const uint64_t *src_present,
                                     const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
+/* fecgpu_rlc_encode_rows_fused / fecgpu_rlc_decode_rows_fused from the host: arguments, staging of the host
+ * arrays and the checks before any launch are those of the *_rows_len_host forms; the sub-batches need
+ * none of the context's packed device buffers (decode uses its plan workspace only). */
+int fecgpu_rlc_encode_rows_fused_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint32_t *src_len,
+                                      const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nblocks,
+                                      uint32_t k, uint32_t r, uint32_t symbol_size, const uint32_t *fbn);
+int fecgpu_rlc_decode_rows_fused_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint32_t *src_len,
+                                      const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                      uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
+                                      const uint32_t *rep_seed, const uint64_t *src_present,
+                                      const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
 /* fecgpu_rlc_window_encode_table from the host: the stream (host rows) crosses PCIe once, by one copy,
  * before the windows are coded from device memory -- a symbol serves up to k windows, so reading it in
  * place would cross the bus that many times; wrow[] is a host array; repairs go to page-locked `rep` in

@@ -43,12 +43,25 @@ def sources():
     return hip, c, hdr
 
 
+GEN = os.path.join(CSRC, "gen_bitslice.py")
+LENS_HDR = os.path.join(CSRC, "bitslice_lens_gen.h")
+
+
+def generate_lens_header(force: bool = False) -> str:
+    """The length-aware decode bodies are generated, not committed (15 bodies, 1.5 MB of text): write
+    csrc/bitslice_lens_gen.h when it is missing or older than the generator.  bitslice_gen.h is left alone."""
+    if force or not os.path.exists(LENS_HDR) or os.path.getmtime(LENS_HDR) < os.path.getmtime(GEN):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("FEC_GEN")}  # the defaults, always
+        _run([sys.executable, GEN, "--lens-only"], env=env)
+    return LENS_HDR
+
+
 def up_to_date() -> bool:
-    if not os.path.exists(LIB):
+    if not os.path.exists(LIB) or not os.path.exists(LENS_HDR):
         return False
     hip, c, hdr = sources()
     t = os.path.getmtime(LIB)
-    return all(os.path.getmtime(f) <= t for f in hip + c + hdr + [__file__])
+    return all(os.path.getmtime(f) <= t for f in hip + c + hdr + [__file__, GEN])
 
 
 def build(force: bool = False, verbose: bool = False, out: str | None = None, defines=()) -> str:
@@ -58,6 +71,7 @@ def build(force: bool = False, verbose: bool = False, out: str | None = None, de
     target = out or LIB
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(os.path.dirname(target), exist_ok=True)
+    generate_lens_header()
     hip, c, _ = sources()
     hipcc = _hipcc()
     objs = []

@@ -22,6 +22,8 @@
  * take a length per row, so every symbol in an arena is still handed over where it lies, for its own
  * length, and only symbols outside every arena are staged (at their own length, no padding).  Against an
  * engine without those two entry points (they are weak references) ragged blocks are staged as before.
+ * Where the engine also has the one-pass forms (fecgpu_rlc_*_rows_fused_host, weak as well) a ragged job
+ * runs through them instead: no packed copy on the device, the kernels read and write the rows themselves.
  * XOR jobs gather too: with a heap registered they run through fecgpu_xor_encode_rows_host /
  * fecgpu_xor_decode_rows_host (one pass, a length per row, no equal-length arm), so every XOR symbol in an
  * arena is read where it lies for its own length, the repair -- and on recover the symbol allocated at
@@ -62,6 +64,13 @@ static int rows_len_available(void) {
 /* So are the XOR row forms: without them an XOR job is staged, packed and zero-padded, whatever is registered. */
 #pragma weak fecgpu_xor_encode_rows_host
 #pragma weak fecgpu_xor_decode_rows_host
+/* And the one-pass ragged RLC forms: with them a ragged job needs none of the engine's packed sub-batch buffers;
+ * without them (the CPU stand-in) it runs through the _rows_len_host forms above. */
+#pragma weak fecgpu_rlc_encode_rows_fused_host
+#pragma weak fecgpu_rlc_decode_rows_fused_host
+static int rows_fused_available(void) {
+    return fecgpu_rlc_encode_rows_fused_host != NULL && fecgpu_rlc_decode_rows_fused_host != NULL;
+}
 static int xor_rows_available(void) {
     return fecgpu_xor_encode_rows_host != NULL && fecgpu_xor_decode_rows_host != NULL;
 }
@@ -509,6 +518,11 @@ static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
                                             j->rec);
     else if (j->gather && j->xor_scheme)
         j->rc = fecgpu_xor_encode_rows_host(c, j->srow, j->slen, j->rrow, j->blen, j->n, j->k, S);
+    else if (j->gather && j->ragged && rows_fused_available() && j->op == OP_RECOVER)
+        j->rc = fecgpu_rlc_decode_rows_fused_host(c, j->srow, j->slen, j->rrow, j->rlen, j->blen, j->n, j->k, j->r, S,
+                                                  j->seeds, j->sp, j->rp, j->st, j->rec);
+    else if (j->gather && j->ragged && rows_fused_available())
+        j->rc = fecgpu_rlc_encode_rows_fused_host(c, j->srow, j->slen, j->rrow, j->blen, j->n, j->k, j->r, S, j->fbn);
     else if (j->gather && j->ragged && j->op == OP_RECOVER)
         j->rc = fecgpu_rlc_decode_rows_len_host(c, j->srow, j->slen, j->rrow, j->rlen, j->blen, j->n, j->k, j->r, S,
                                                 j->seeds, j->sp, j->rp, j->st, j->rec);

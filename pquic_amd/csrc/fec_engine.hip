@@ -44,6 +44,12 @@
 #include "bitslice_gen.h"
 #endif
 #endif
+// the length-aware decode bodies: written by the build (gen_bitslice.py --lens-only), not kept in the repository
+#ifdef FEC_GEN_LENS_HDR  // beside FEC_GEN_HDR
+#include FEC_GEN_LENS_HDR
+#else
+#include "bitslice_lens_gen.h"
+#endif
 #include "../../include/fecgpu.h"
 #include "fecgpu_internal.h"
 
@@ -1565,6 +1571,20 @@ struct BsLanes {
                         ln.vm[4], ln.vm[5], ln.vm[6], ln.vm[7]);                                    \
   } while (0)
 
+// the length-aware bodies (bs_decl_*): the same arguments, table entries with a byte bound in bits 48-63
+#define BS_CALL_DECL(RT)                                                                            \
+  do {                                                                                              \
+    if constexpr (VEC == 16)                                                                        \
+      bs_decl_r##RT##_v16(ia, oa, nsrc, k, ca, ln.off[0], ln.off[1], ln.vm[0], ln.vm[1]);           \
+    else if constexpr (VEC == 8)                                                                    \
+      bs_decl_r##RT##_v8(ia, oa, nsrc, k, ca, ln.off[0], ln.off[1], ln.off[2], ln.off[3], ln.vm[0], \
+                         ln.vm[1], ln.vm[2], ln.vm[3]);                                             \
+    else                                                                                            \
+      bs_decl_r##RT##_v4(ia, oa, nsrc, k, ca, ln.off[0], ln.off[1], ln.off[2], ln.off[3], ln.off[4], \
+                         ln.off[5], ln.off[6], ln.off[7], ln.vm[0], ln.vm[1], ln.vm[2], ln.vm[3],   \
+                         ln.vm[4], ln.vm[5], ln.vm[6], ln.vm[7]);                                   \
+  } while (0)
+
 template <int RT, int VEC>
 __device__ __forceinline__ void bs_enc_call(uint64_t sp, uint64_t rpp, uint32_t L, uint64_t rstep, uint64_t sdelta,
                                             uint32_t nsrc, uint32_t k, uint32_t rt, uint32_t ca,
@@ -1587,6 +1607,23 @@ __device__ __forceinline__ void bs_dec_call(uint32_t ia, uint32_t oa, uint32_t n
   else if constexpr (RT == 8) BS_CALL_DEC(8);
   else BS_CALL_DEC(16);
 }
+
+template <int RT, int VEC>
+__device__ __forceinline__ void bs_decl_call(uint32_t ia, uint32_t oa, uint32_t nsrc, uint32_t k, uint32_t ca,
+                                             const BsLanes<VEC> &ln) {
+  if constexpr (RT == 1) BS_CALL_DECL(1);
+  else if constexpr (RT == 2) BS_CALL_DECL(2);
+  else if constexpr (RT == 4) BS_CALL_DECL(4);
+  else if constexpr (RT == 8) BS_CALL_DECL(8);
+  else BS_CALL_DECL(16);
+}
+
+// Table entry of the length-aware bodies: the row's address (48 bits) under the number of its bytes
+// that count (<= 65532).  A row of 0 bytes gets entry 0: its address is never looked at.
+__device__ __forceinline__ uint64_t row_entry(uint64_t addr, uint32_t n) {
+  return n ? (addr & 0xffffffffffffull) | ((uint64_t)n << 48) : 0ull;
+}
+__device__ __forceinline__ uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 // Blocks per group: at most 64 / RT (one coefficient lane per (block, repair)), bounded by the LDS
 // budget.  Defaults measured in-process (profiles/r01_ab_group.log, three boxes; r02_ab_group*.log):
@@ -1748,12 +1785,16 @@ __device__ __forceinline__ uint64_t rec_row(uint64_t b, int k, int j, int dst_ro
 // wave calls it.  dst_rows < 0: row tables (fecgpu_rlc_decode_rows) -- src and rep are the [block][k]
 // source-row and [block][r] repair-row device-address tables, and a missing source's entry is the row
 // its recovered bytes go to.  k_rlc_recover_bs runs it over a grid-stride loop; k_rlc_decode_small after the
-// wave plan of the group's block.
-template <int RT, int VEC>
+// wave plan of the group's block.  LEN (row tables only, fecgpu_rlc_decode_rows_fused): every row counts for
+// its own length -- an input for min(its length, blk_len[b]), an output for blk_len[b] bytes, both
+// clamped to L -- through the length-aware bodies.
+template <int RT, int VEC, bool LEN = false>
 __device__ void recover_bs_group(uint64_t q, uint64_t NG, uint64_t bstep, uint8_t *__restrict__ src,
                                  const uint8_t *__restrict__ rep, uint64_t nblocks, int k, int r, int L, int nchunks,
                                  int chunk_bytes, uint8_t *ws, int r0, int G, uint8_t *status, uint64_t *recovered,
-                                 int ilv, uint8_t *dst, uint8_t *lds, uint8_t *wsl = nullptr, int dst_rows = 0) {
+                                 int ilv, uint8_t *dst, uint8_t *lds, uint8_t *wsl = nullptr, int dst_rows = 0,
+                                 const uint32_t *src_len = nullptr, const uint32_t *rep_len = nullptr,
+                                 const uint32_t *blk_len = nullptr) {
   const WsLayout WL = ws_layout((uint32_t)k, (uint32_t)r);
   const int lane = threadIdx.x;
   RecoverLds<RT> S(lds, G, k);
@@ -1830,7 +1871,12 @@ __device__ void recover_bs_group(uint64_t q, uint64_t NG, uint64_t bstep, uint8_
 #endif
       const uint32_t sl = h[WL.off_slot + j];
 #endif
-      if (dst_rows < 0) {  // row tables: src / rep hold the rows' device addresses ([block][k] / [block][r])
+      if constexpr (LEN) {
+        const uint32_t bl = min_u32(blk_len[b], (uint32_t)L);
+        const uint64_t ri = (sl & 0x80) ? b * (uint64_t)r + (sl & 0x7f) : b * (uint64_t)k + sl;
+        const uint32_t n = min_u32((sl & 0x80) ? rep_len[ri] : src_len[ri], bl);
+        S.intab[x] = row_entry(reinterpret_cast<const uint64_t *>((sl & 0x80) ? rep : src)[ri], n);
+      } else if (dst_rows < 0) {  // row tables: src / rep hold the rows' device addresses ([block][k] / [block][r])
         S.intab[x] = (sl & 0x80) ? reinterpret_cast<const uint64_t *>(rep)[b * (uint64_t)r + (sl & 0x7f)]
                                  : reinterpret_cast<const uint64_t *>(src)[b * (uint64_t)k + sl];
       } else {
@@ -1853,9 +1899,14 @@ __device__ void recover_bs_group(uint64_t q, uint64_t NG, uint64_t bstep, uint8_
 #else
         const int j = h[WL.off_unk + r0 + u];
 #endif
-        reinterpret_cast<uint64_t *>(rc)[u] =
-            dst_rows < 0 ? reinterpret_cast<const uint64_t *>(src)[b * (uint64_t)k + j]  // the missing source's row
-                         : (uint64_t)(uintptr_t)(dst + rec_row(b, k, j, dst_rows, r0 + u) * (uint64_t)L);
+        if constexpr (LEN) {
+          reinterpret_cast<uint64_t *>(rc)[u] =
+              row_entry(reinterpret_cast<const uint64_t *>(src)[b * (uint64_t)k + j], min_u32(blk_len[b], (uint32_t)L));
+        } else {
+          reinterpret_cast<uint64_t *>(rc)[u] =
+              dst_rows < 0 ? reinterpret_cast<const uint64_t *>(src)[b * (uint64_t)k + j]  // the missing source's row
+                           : (uint64_t)(uintptr_t)(dst + rec_row(b, k, j, dst_rows, r0 + u) * (uint64_t)L);
+        }
         if (status) {
           uint32_t m = 0;
 #ifndef FEC_PROBE_NOWS
@@ -1881,10 +1932,12 @@ __device__ void recover_bs_group(uint64_t q, uint64_t NG, uint64_t bstep, uint8_
         for (int q = 0; q < BsLanes<VEC>::NP; q++) ln.off[q] += (uint32_t)c0;  // chunk offset
         // nsrc and k go to SGPRs: readfirstlane states their uniformity (a plan inlined into a
         // one-lane branch before this call can leave the compiler unsure of it)
-        if (lane < ln.active)
-          bs_dec_call<RT, VEC>(lds_addr(S.intab), lds_addr(S.rec),
-                               (uint32_t)__builtin_amdgcn_readfirstlane(nact * k),
-                               (uint32_t)__builtin_amdgcn_readfirstlane(k), lds_addr(S.coef), ln);
+        if (lane < ln.active) {
+          const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane(nact * k);
+          const uint32_t ku = (uint32_t)__builtin_amdgcn_readfirstlane(k);
+          if constexpr (LEN) bs_decl_call<RT, VEC>(lds_addr(S.intab), lds_addr(S.rec), ns, ku, lds_addr(S.coef), ln);
+          else bs_dec_call<RT, VEC>(lds_addr(S.intab), lds_addr(S.rec), ns, ku, lds_addr(S.coef), ln);
+        }
       }
     }
     __syncthreads();
@@ -1944,17 +1997,37 @@ void k_rlc_recover_bs(uint8_t *__restrict__ src, const uint8_t *__restrict__ rep
                               recovered, ilv, dst, lds, wsl_off ? lds + wsl_off : nullptr, dst_rows);
 }
 
+// The recover pass of fecgpu_rlc_decode_rows_fused: row tables and a length per row, one group per workgroup
+template <int RT, int VEC>
+__global__ __launch_bounds__(64) void k_rlc_recover_rows_fused(
+    uint8_t *__restrict__ src_rows, const uint8_t *__restrict__ rep_rows, const uint32_t *__restrict__ src_len,
+    const uint32_t *__restrict__ rep_len, const uint32_t *__restrict__ blk_len, uint64_t nblocks, int k, int r, int L,
+    int nchunks, int chunk_bytes, uint8_t *ws, int r0, int G, uint8_t *status, uint64_t *recovered, int ilv,
+    uint32_t wsl_off, uint64_t q0) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  const uint64_t NG = (nblocks + G - 1) / G;
+  const uint64_t bstep = (ilv & 1) ? NG : 1;
+  const uint64_t q = q0 + grp_index(ilv);
+  if (q < NG)
+    recover_bs_group<RT, VEC, true>(q, NG, bstep, src_rows, rep_rows, nblocks, k, r, L, nchunks, chunk_bytes, ws, r0, G,
+                                    status, recovered, ilv, nullptr, lds, wsl_off ? lds + wsl_off : nullptr, -1,
+                                    src_len, rep_len, blk_len);
+}
+
 // Encode with the rows given by address (fecgpu_rlc_encode_rows): the batching adapter hands the
 // kernel the symbols where they lie -- the FEC plugin's registered memory arena -- instead of copying
 // them into a packed batch.  src_rows[b * k + j] / rep_rows[b * r + i]: device addresses of source row
 // j / repair row i of block b.  Same data body as the recover pass (input addresses and output records
 // staged in LDS per group), with the coefficients from TinyMT32 as in k_rlc_encode_bs.
-template <int RT, int VEC>
-__global__ __launch_bounds__(64) void k_rlc_encode_rows(const uint64_t *__restrict__ src_rows,
-                                                        const uint64_t *__restrict__ rep_rows, uint64_t nblocks, int k,
-                                                        int r, int L, int nchunks, int chunk_bytes, uint32_t fbn_base,
-                                                        const uint32_t *fbn, int r0, int G) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+// LEN (fecgpu_rlc_encode_rows_fused): source row x counts for min(src_len[x], blk_len[b]) bytes and every
+// repair row of block b gets blk_len[b] bytes, both clamped to L, through the length-aware bodies.
+template <int RT, int VEC, bool LEN>
+__device__ __forceinline__ void encode_rows_groups(const uint64_t *__restrict__ src_rows,
+                                                   const uint64_t *__restrict__ rep_rows, uint64_t nblocks, int k,
+                                                   int r, int L, int nchunks, int chunk_bytes, uint32_t fbn_base,
+                                                   const uint32_t *fbn, int r0, int G, uint8_t *lds,
+                                                   const uint32_t *__restrict__ src_len,
+                                                   const uint32_t *__restrict__ blk_len) {
   RecoverLds<RT> S(lds, G, k);
   constexpr int CSB = RecoverLds<RT>::CSB;
   const int lane = threadIdx.x;
@@ -1981,12 +2054,22 @@ __global__ __launch_bounds__(64) void k_rlc_encode_rows(const uint64_t *__restri
             for (int x = RT; x < 4; x++) row0[j * (CSB / 2) + FEC_BS_FIELD_SLOT(RT, x)] = 0;
       }
     }
-    for (int x = lane; x < ng * k; x += 64) S.intab[x] = src_rows[b0 * k + x];
+    for (int x = lane; x < ng * k; x += 64) {
+      if constexpr (LEN)
+        S.intab[x] = row_entry(src_rows[b0 * k + x],
+                               min_u32(src_len[b0 * k + x], min_u32(blk_len[b0 + x / k], (uint32_t)L)));
+      else
+        S.intab[x] = src_rows[b0 * k + x];
+    }
     for (int x = lane; x < ng * 16; x += 64) {
       const int t = x >> 4, u = x & 15;
       uint8_t *rc = S.rec + (size_t)t * kDecRec;
       rc[kDecRecNz + u] = 0;
-      if (u < rt) reinterpret_cast<uint64_t *>(rc)[u] = rep_rows[(b0 + t) * r + r0 + u];
+      if (u < rt) {
+        const uint64_t row = rep_rows[(b0 + t) * r + r0 + u];
+        if constexpr (LEN) reinterpret_cast<uint64_t *>(rc)[u] = row_entry(row, min_u32(blk_len[b0 + t], (uint32_t)L));
+        else reinterpret_cast<uint64_t *>(rc)[u] = row;
+      }
       if (u == 0) reinterpret_cast<uint32_t *>(rc)[kDecRecRt] = (uint32_t)rt;
     }
     __syncthreads();
@@ -1996,11 +2079,34 @@ __global__ __launch_bounds__(64) void k_rlc_encode_rows(const uint64_t *__restri
       BsLanes<VEC> ln(lane, cb);
 #pragma unroll
       for (int x = 0; x < BsLanes<VEC>::NP; x++) ln.off[x] += (uint32_t)c0;
-      if (lane < ln.active)
-        bs_dec_call<RT, VEC>(lds_addr(S.intab), lds_addr(S.rec), (uint32_t)__builtin_amdgcn_readfirstlane(ng * k),
-                             (uint32_t)__builtin_amdgcn_readfirstlane(k), lds_addr(S.coef), ln);
+      if (lane < ln.active) {
+        const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane(ng * k);
+        const uint32_t ku = (uint32_t)__builtin_amdgcn_readfirstlane(k);
+        if constexpr (LEN) bs_decl_call<RT, VEC>(lds_addr(S.intab), lds_addr(S.rec), ns, ku, lds_addr(S.coef), ln);
+        else bs_dec_call<RT, VEC>(lds_addr(S.intab), lds_addr(S.rec), ns, ku, lds_addr(S.coef), ln);
+      }
     }
   }
+}
+
+template <int RT, int VEC>
+__global__ __launch_bounds__(64) void k_rlc_encode_rows(const uint64_t *__restrict__ src_rows,
+                                                        const uint64_t *__restrict__ rep_rows, uint64_t nblocks, int k,
+                                                        int r, int L, int nchunks, int chunk_bytes, uint32_t fbn_base,
+                                                        const uint32_t *fbn, int r0, int G) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  encode_rows_groups<RT, VEC, false>(src_rows, rep_rows, nblocks, k, r, L, nchunks, chunk_bytes, fbn_base, fbn, r0, G,
+                                     lds, nullptr, nullptr);
+}
+
+template <int RT, int VEC>
+__global__ __launch_bounds__(64) void k_rlc_encode_rows_fused(
+    const uint64_t *__restrict__ src_rows, const uint32_t *__restrict__ src_len, const uint64_t *__restrict__ rep_rows,
+    const uint32_t *__restrict__ blk_len, uint64_t nblocks, int k, int r, int L, int nchunks, int chunk_bytes,
+    uint32_t fbn_base, const uint32_t *fbn, int r0, int G) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  encode_rows_groups<RT, VEC, true>(src_rows, rep_rows, nblocks, k, r, L, nchunks, chunk_bytes, fbn_base, fbn, r0, G,
+                                    lds, src_len, blk_len);
 }
 
 // Decode of a few blocks in ONE launch (the synchronous hooks decode one block per call): each
@@ -2406,27 +2512,37 @@ static void launch_encode_bs(const uint8_t *src, uint8_t *rep, uint64_t nb, int 
                     c.nchunks, c.chunk_bytes, fbn_base, fbn, r0, G, sbs, fbn_step, interleave_groups(), bw)
 }
 
+// Launch shape of a recover data pass (k_rlc_recover_bs, k_rlc_recover_rows_fused): blocks per group, groups,
+// dynamic LDS, and where in it the group's workspace records are staged (0: not staged)
+struct RecoverShape { int G; uint64_t groups; size_t lds; uint32_t wsl_off; };
+template <int RT>
+static RecoverShape recover_shape(uint64_t nb, int k, int r, const BsCfg &c, const uint8_t *ws) {
+  RecoverShape h;
+  h.G = bs_group(RT, k, FEC_BS_COEF_ROW_BYTES(RT) + 8, kDecRec + 80, false, c.nchunks, nb);
+  h.lds = RecoverLds<RT>::bytes(h.G, k);
+  // the group's workspace records staged in LDS by one round trip (knob ws_lds) when they are small
+  const size_t wsb = (size_t)h.G * ws_layout((uint32_t)k, (uint32_t)r).stride;
+  h.wsl_off = 0;
+  if (knob(K_WS_LDS) && wsb <= kWsLdsMax && ((uintptr_t)ws & 15) == 0) {
+    h.wsl_off = (uint32_t)((h.lds + 15) & ~(size_t)15);
+    h.lds = h.wsl_off + wsb;
+  }
+  h.groups = (nb + h.G - 1) / h.G;
+  // knob dec_waves = n: at most n waves per SIMD (the workgroup's LDS sized so 4 n fit a CU's 160 KiB)
+  if (const int dw = knob(K_DEC_WAVES)) {
+    const size_t cap = (size_t)160 * 1024 / (4 * (size_t)dw) & ~(size_t)15;
+    if (h.lds < cap) h.lds = cap;
+  }
+  return h;
+}
+
 template <int RT, int VEC>
 static void launch_recover_bs(uint8_t *src, const uint8_t *rep, uint64_t nb, int k, int r, int L, const BsCfg &c,
                               uint8_t *ws, int r0, uint8_t *status, uint64_t *recovered, hipStream_t s,
                               uint8_t *dst, int dst_rows) {
-  const int G = bs_group(RT, k, FEC_BS_COEF_ROW_BYTES(RT) + 8, kDecRec + 80, false, c.nchunks, nb);
-  size_t lds = RecoverLds<RT>::bytes(G, k);
-  // the group's workspace records staged in LDS by one round trip (knob ws_lds) when they are small
-  const size_t wsb = (size_t)G * ws_layout((uint32_t)k, (uint32_t)r).stride;
-  uint32_t wsl_off = 0;
-  if (knob(K_WS_LDS) && wsb <= kWsLdsMax && ((uintptr_t)ws & 15) == 0) {
-    wsl_off = (uint32_t)((lds + 15) & ~(size_t)15);
-    lds = wsl_off + wsb;
-  }
-  const uint64_t groups = (nb + G - 1) / G;
-  // knob dec_waves = n: at most n waves per SIMD (the workgroup's LDS sized so 4 n fit a CU's 160 KiB)
-  if (const int dw = knob(K_DEC_WAVES)) {
-    const size_t cap = (size_t)160 * 1024 / (4 * (size_t)dw) & ~(size_t)15;
-    if (lds < cap) lds = cap;
-  }
-  FEC_LAUNCH_GROUPS((k_rlc_recover_bs<RT, VEC>), groups, 64, lds, s, src, rep, nb, k, r, L, c.nchunks,
-                    c.chunk_bytes, ws, r0, G, status, recovered, interleave_groups(), dst, wsl_off, dst_rows)
+  const RecoverShape h = recover_shape<RT>(nb, k, r, c, ws);
+  FEC_LAUNCH_GROUPS((k_rlc_recover_bs<RT, VEC>), h.groups, 64, h.lds, s, src, rep, nb, k, r, L, c.nchunks,
+                    c.chunk_bytes, ws, r0, h.G, status, recovered, interleave_groups(), dst, h.wsl_off, dst_rows)
 }
 
 template <int RT, int VEC>
@@ -2435,6 +2551,28 @@ static void launch_encode_rows(const uint64_t *src_rows, const uint64_t *rep_row
   const int G = bs_group(RT, k, FEC_BS_COEF_ROW_BYTES(RT) + 8, kDecRec + 80, false, c.nchunks, nb);
   hipLaunchKernelGGL((k_rlc_encode_rows<RT, VEC>), dim3(grid_for((nb + G - 1) / G)), dim3(64), RecoverLds<RT>::bytes(G, k),
                      s, src_rows, rep_rows, nb, k, r, L, c.nchunks, c.chunk_bytes, fbn_base, fbn, r0, G);
+}
+
+template <int RT, int VEC>
+static void launch_encode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                     const uint32_t *blk_len, uint64_t nb, int k, int r, int L, const BsCfg &c,
+                                     uint32_t fbn_base, const uint32_t *fbn, int r0, hipStream_t s) {
+  const int G = bs_group(RT, k, FEC_BS_COEF_ROW_BYTES(RT) + 8, kDecRec + 80, false, c.nchunks, nb);
+  hipLaunchKernelGGL((k_rlc_encode_rows_fused<RT, VEC>), dim3(grid_for((nb + G - 1) / G)), dim3(64),
+                     RecoverLds<RT>::bytes(G, k), s, src_rows, src_len, rep_rows, blk_len, nb, k, r, L, c.nchunks,
+                     c.chunk_bytes, fbn_base, fbn, r0, G);
+}
+
+// as launch_recover_bs, on row tables with a length per row
+template <int RT, int VEC>
+static void launch_recover_rows_fused(const uint64_t *src_rows, const uint64_t *rep_rows, const uint32_t *src_len,
+                                      const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nb, int k, int r,
+                                      int L, const BsCfg &c, uint8_t *ws, int r0, uint8_t *status,
+                                      uint64_t *recovered, hipStream_t s) {
+  const RecoverShape h = recover_shape<RT>(nb, k, r, c, ws);
+  FEC_LAUNCH_GROUPS((k_rlc_recover_rows_fused<RT, VEC>), h.groups, 64, h.lds, s, (uint8_t *)src_rows,
+                    (const uint8_t *)rep_rows, src_len, rep_len, blk_len, nb, k, r, L, c.nchunks, c.chunk_bytes, ws, r0,
+                    h.G, status, recovered, interleave_groups(), h.wsl_off)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4193,6 +4331,56 @@ int fecgpu_rlc_decode_rows_len(const uint64_t *src_rows, const uint32_t *src_len
   return fecgpu_rlc_decode_rows_len_internal(src_rows, src_len, rep_rows, rep_len, blk_len, nblocks, k, r,
                                              symbol_size, rep_seed, src_present, rep_present, status, recovered, ws,
                                              ws + W.rep, ws + W.rec, ws + W.dec, W.total - W.dec, stream);
+}
+
+// ---- ragged rows in one pass (the length-aware bodies; no packed intermediate) ----
+int fecgpu_rlc_encode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                 const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r,
+                                 uint32_t symbol_size, uint32_t fbn_base, const uint32_t *fbn, void *stream) {
+  int rc = check_common(src_rows, rep_rows, nblocks, k, r, symbol_size);
+  if (rc || nblocks == 0 || r == 0) return rc;
+  if (!src_len || !blk_len) return set_err(FECGPU_ERR_INVALID, "%s", "NULL length table");
+  if (int rc2 = bs_table_check()) return rc2;
+  hipStream_t s = (hipStream_t)stream;
+  const BsCfg cfg = pick_bs_cfg((int)symbol_size);
+  const int rt = pick_rt(r);
+  for (int r0 = 0; r0 < (int)r; r0 += rt) {
+    FEC_BS_DISPATCH(launch_encode_rows_fused, src_rows, src_len, rep_rows, blk_len, nblocks, (int)k, (int)r,
+                    (int)symbol_size, cfg, fbn_base, fbn, r0, s)
+  }
+  HIPCHK(hipGetLastError());
+  count_encode(nblocks);
+  return FECGPU_OK;
+}
+
+int fecgpu_rlc_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                 const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                 uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                 const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                 uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream) {
+  int rc = decode_args(src_rows, rep_rows, nblocks, k, r, symbol_size, src_present, rep_present, status, recovered,
+                       workspace, workspace_bytes);
+  if (rc || nblocks == 0) return rc;
+  if (!src_len || !blk_len || (r && !rep_len)) return set_err(FECGPU_ERR_INVALID, "%s", "NULL length table");
+  if (r && !rep_seed) return set_err(FECGPU_ERR_INVALID, "%s", "NULL rep_seed");
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = decode_plan_impl(nblocks, k, r, 0, nullptr, rep_seed, src_present, rep_present, workspace,
+                             workspace_bytes, s)))
+    return rc;
+  count_decode(nblocks);
+  uint8_t *ws = (uint8_t *)workspace;
+  const WsLayout WL = ws_layout(k, r);
+  if (r == 0) return launch_finalize(nblocks, k, r, status, recovered, ws, s);
+  if (int rc2 = bs_table_check()) return rc2;
+  const int rt = decode_tile(WL.em);
+  const BsCfg cfg = pick_bs_cfg((int)symbol_size);
+  const bool fused = (int)WL.em <= rt;
+  for (int r0 = 0; r0 < (int)WL.em; r0 += rt) {
+    FEC_BS_DISPATCH(launch_recover_rows_fused, src_rows, rep_rows, src_len, rep_len, blk_len, nblocks, (int)k, (int)r,
+                    (int)symbol_size, cfg, ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s)
+  }
+  HIPCHK(hipGetLastError());
+  return fused ? FECGPU_OK : launch_finalize(nblocks, k, r, status, recovered, ws, s);
 }
 
 // host_path.hip's argument errors (library-internal): the message fecgpu_last_error() returns

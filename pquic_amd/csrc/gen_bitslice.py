@@ -37,6 +37,10 @@ import random
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.environ.get("FEC_GEN_OUT") or os.path.join(HERE, "bitslice_gen.h")
+# The length-aware decode bodies (bs_decl_*) go to a header of their own beside OUT.  It is not kept in the
+# repository: pquic_amd/build.py writes it before it compiles (`gen_bitslice.py --lens-only`, which leaves
+# OUT alone), and fec_engine.hip includes it after OUT, whose macros and case table it uses.
+OUT_LENS = os.path.join(os.path.dirname(OUT), "bitslice_lens_gen.h")
 
 # ----------------------------------------------------------------------------- register map
 # T64: the exchange rounds shift two words per instruction (v_lshlrev_b64 / v_lshrrev_b64 on an
@@ -443,20 +447,249 @@ def regrange(base, n):
     return f"v{base}" if n == 1 else f"v[{base}:{base + n - 1}]"
 
 
-def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False):
+# ============================================================================ rows of their own length
+# The length-aware decode bodies (bs_decl_*).  Every 64-bit table entry carries, above its 48 address
+# bits, the number of bytes that count: an input row's min(len, blk_len), an output row's blk_len.
+# * Loads go through a buffer descriptor built per row from wave-uniform values (base = the entry's
+#   address, stride 0, num_records = the bound rounded up to 4): the range check returns zeros for
+#   every dword at or past it, reads nothing there, and reads nothing at all of a row of 0 bytes.
+#   num_records and all offsets are multiples of 4, so no dword straddles the bound.
+# * The 1-3 foreign bytes of the dword that holds a row's last byte are cleared before the transpose,
+#   in a wave-uniform branch taken only when the bound is no multiple of 4: per lane dword one
+#   v_cmpx (the lanes whose piece holds that dword) and one v_and -- 16 VALU per such source row.
+# * Stores: dword stores through a descriptor of num_records = blk_len & ~3, then, when blk_len & 3,
+#   the lanes that hold the last dword store its bytes one by one through a descriptor of exactly
+#   blk_len bytes, whose (per byte) range check drops those past the row.  No read-modify-write.
+# The consumed row's bound is read from the input table a step ahead through v69 (the hole below
+# NADDR) and an SGPR pointer, so the variant needs no VGPR beyond the 'dec' bodies'.
+S_LD, S_SD = 92, 96     # load / store descriptors s[92:95], s[96:99] (S_DJ and up: free in 'dec')
+S_LENP = S_JL           # LDS address of the next table entry whose bound is read
+S_LEN, S_SCC = S_OUT, S_OUT + 1  # bound of the row being consumed; the refill decision kept across SALU
+S_TA, S_TM = S_O2, S_O2 + 1      # offset of the tail dword, its byte mask / blk_len
+LENV = 69
+SRD_WORD3 = 0x00020000
+SGPR_CLOBBER_LENS = list(range(94, 100))
+BUFOP = {16: ("buffer_load_dwordx4", "buffer_store_dwordx4"), 8: ("buffer_load_dwordx2", "buffer_store_dwordx2"),
+         4: ("buffer_load_dword", "buffer_store_dword")}
+
+
+def lens_loads(VEC, data0):
+    """Descriptor of the row whose table entry sits in s[S_LD:S_LD+1], then the lane's loads."""
+    nw, NP = LOADOP[VEC][2], 32 // VEC
+    out = [f"s_lshr_b32 s{S_LD + 2}, s{S_LD + 1}, 16",
+           f"s_and_b32 s{S_LD + 1}, s{S_LD + 1}, 0xffff",
+           f"s_add_u32 s{S_LD + 2}, s{S_LD + 2}, 3",
+           f"s_andn2_b32 s{S_LD + 2}, s{S_LD + 2}, 3"]
+    for q in range(NP):
+        out.append(f"{BUFOP[VEC][0]} {regrange(data0 + q * nw, nw)}, %[off{q}], s[{S_LD}:{S_LD + 3}], 0 offen@LDPOL@")
+    return out
+
+
+def lens_tail_mask(VEC, data0, live, tag):
+    """Zero the bytes at and past the bound s{S_LEN} in the dword that holds them (data in data0..+7)."""
+    nw = LOADOP[VEC][2]
+    out = [f"s_and_b32 s{S_TM}, s{S_LEN}, 3",
+           f"s_cbranch_scc0 .Lnotail_{tag}_%=",
+           f"s_andn2_b32 s{S_TA}, s{S_LEN}, 3",
+           f"s_lshl_b32 s{S_TM}, s{S_TM}, 3",
+           f"s_bfm_b32 s{S_TM}, s{S_TM}, 0"]
+    for w in range(8):
+        q, d = divmod(w, nw)
+        out += [f"s_sub_u32 s{S_CQ}, s{S_TA}, {4 * d}",  # a borrow wraps far above every offset
+                f"v_cmpx_eq_u32 vcc, s{S_CQ}, %[off{q}]",
+                f"v_and_b32 v{data0 + w}, s{S_TM}, v{data0 + w}",
+                f"s_mov_b64 exec, {live}"]
+    out.append(f".Lnotail_{tag}_%=:")
+    return out
+
+
+def lens_stores(VEC, accs, live, tag):
+    """Exactly blk_len bytes of the row in accs to the row whose table entry sits in s[S_SD:S_SD+1]."""
+    nw, NP = LOADOP[VEC][2], 32 // VEC
+    out = [f"s_lshr_b32 s{S_TM}, s{S_SD + 1}, 16",
+           f"s_and_b32 s{S_SD + 1}, s{S_SD + 1}, 0xffff",
+           f"s_andn2_b32 s{S_SD + 2}, s{S_TM}, 3",
+           "s_nop 1"]  # word 0 came from a v_readfirstlane: five wait states before a VMEM instruction reads it
+    for q in range(NP):
+        out += [f"s_mov_b64 exec, %[vm{q}]",
+                f"{BUFOP[VEC][1]} {regrange(accs[q * nw], nw)}, %[off{q}], s[{S_SD}:{S_SD + 3}], 0 offen@STPOL@"]
+    out += [f"s_and_b32 s{S_TA}, s{S_TM}, 3",
+            f"s_cbranch_scc0 .Lnost_{tag}_%=",
+            f"s_andn2_b32 s{S_TA}, s{S_TM}, 3",
+            f"s_mov_b32 s{S_SD + 2}, s{S_TM}"]
+    for w in range(8):
+        q, d = divmod(w, nw)
+        out += [f"s_sub_u32 s{S_T3}, s{S_TA}, {4 * d}",
+                f"s_mov_b64 exec, %[vm{q}]",
+                f"v_cmpx_eq_u32 vcc, s{S_T3}, %[off{q}]",
+                f"buffer_store_byte v{accs[w]}, %[off{q}], s[{S_SD}:{S_SD + 3}], 0 offen offset:{4 * d}@STPOL@",
+                f"v_lshrrev_b32 v{TMP[0]}, 8, v{accs[w]}",
+                f"buffer_store_byte v{TMP[0]}, %[off{q}], s[{S_SD}:{S_SD + 3}], 0 offen offset:{4 * d + 1}@STPOL@",
+                f"buffer_store_byte_d16_hi v{accs[w]}, %[off{q}], s[{S_SD}:{S_SD + 3}], 0 offen offset:{4 * d + 2}@STPOL@"]
+    out += [f".Lnost_{tag}_%=:", f"s_mov_b64 exec, {live}"]
+    return out
+
+
+def lanes_model(VEC, cb):
+    """BsLanes of fec_engine.hip: per lane the NP piece offsets and whether the lane owns each piece."""
+    NP = 32 // VEC
+    npieces = (cb + VEC - 1) // VEC
+    active = (npieces + NP - 1) // NP
+    off, ok = [], []
+    for lane in range(64):
+        o, k = [], []
+        for q in range(NP):
+            piece = lane + active * q
+            good = lane < active and piece < npieces
+            k.append(good)
+            o.append((piece * VEC if piece * VEC < cb - VEC else cb - VEC) if good else 0)
+        off.append(o)
+        ok.append(k)
+    return off, ok, active
+
+
+def simulate_lens(lines, sg, vg, off, ok, live, mem, readable):
+    """Run the instructions lens_loads / lens_tail_mask / lens_stores emit on 64 lanes.  sg: SGPRs,
+    vg[lane]: VGPRs, mem: the row's bytes (a bytearray, loads and stores), readable: bytes a load may
+    touch.  Buffer accesses are range-checked per dword (per byte for byte stores) against word 2."""
+    import re
+    M = 0xFFFFFFFF
+    ex = list(live)
+    scc = 0
+    sv = lambda t: sg[int(t[1:])] if t.startswith("s") else int(t, 0)  # noqa: E731
+    labels = {ln[:-1]: i for i, ln in enumerate(lines) if ln.endswith(":")}
+    pc = 0
+    while pc < len(lines):
+        ln = lines[pc].replace("@LDPOL@", "").replace("@STPOL@", "")
+        pc += 1
+        if ln.endswith(":"):
+            continue
+        op, _, rest = ln.partition(" ")
+        a = [x.strip() for x in rest.split(",")]
+        if op in ("s_and_b32", "s_andn2_b32", "s_lshl_b32", "s_lshr_b32", "s_bfm_b32", "s_sub_u32", "s_add_u32"):
+            x, y = sv(a[1]), sv(a[2])
+            res = {"s_and_b32": x & y, "s_andn2_b32": x & ~y, "s_lshl_b32": x << (y & 31), "s_lshr_b32": x >> (y & 31),
+                   "s_bfm_b32": ((1 << (x & 31)) - 1) << (y & 31), "s_sub_u32": x - y, "s_add_u32": x + y}[op]
+            if op != "s_bfm_b32":  # the only one of them that leaves SCC alone
+                scc = int(res < 0 or res > M) if op in ("s_sub_u32", "s_add_u32") else int(res & M != 0)
+            sg[int(a[0][1:])] = res & M
+        elif op == "s_nop":
+            pass
+        elif op == "s_mov_b32":
+            sg[int(a[0][1:])] = sv(a[1])
+        elif op == "s_mov_b64":
+            assert a[0] == "exec", ln
+            p = re.match(r"%\[vm(\d+)\]", a[1])
+            ex = [ok[l][int(p.group(1))] for l in range(64)] if p else list(live)
+        elif op == "s_cbranch_scc0":
+            if not scc:
+                pc = labels[a[0]]
+        elif op == "v_cmpx_eq_u32":
+            q = int(re.match(r"%\[off(\d+)\]", a[2]).group(1))
+            ex = [ex[l] and sv(a[1]) == off[l][q] for l in range(64)]
+        elif op == "v_and_b32":
+            for l in range(64):
+                if ex[l]:
+                    vg[l][int(a[0][1:])] = sv(a[1]) & vg[l][int(a[2][1:])]
+        elif op == "v_lshrrev_b32":
+            for l in range(64):
+                if ex[l]:
+                    vg[l][int(a[0][1:])] = vg[l][int(a[2][1:])] >> sv(a[1])
+        else:
+            p = re.match(r"v\[(\d+):(\d+)\]|v(\d+)", a[0])
+            r0 = int(p.group(1) or p.group(3))
+            n = int(p.group(2)) - r0 + 1 if p.group(2) else 1
+            q = int(re.match(r"%\[off(\d+)\]", a[1]).group(1))
+            d0 = int(re.match(r"s\[(\d+):", a[2]).group(1))
+            assert a[3].startswith("0 offen") and sg[d0 + 1] >> 16 == 0 and sg[d0 + 3] == SRD_WORD3, ln
+            io = re.search(r"offset:(\d+)", a[3])
+            io = int(io.group(1)) if io else 0
+            nrec = sg[d0 + 2]
+            for l in range(64):
+                if not ex[l]:
+                    continue
+                o = off[l][q] + io
+                if op.startswith("buffer_load_dword"):
+                    for i in range(n):
+                        assert (o + 4 * i) % 4 == 0 and nrec % 4 == 0
+                        if o + 4 * i < nrec:
+                            assert all(readable[o + 4 * i + t] for t in range(4)), ("read outside the row", o + 4 * i)
+                            vg[l][r0 + i] = int.from_bytes(mem[o + 4 * i:o + 4 * i + 4], "little")
+                        else:
+                            vg[l][r0 + i] = 0
+                elif op.startswith("buffer_store_dword"):
+                    for i in range(n):
+                        assert (o + 4 * i) % 4 == 0 and nrec % 4 == 0
+                        if o + 4 * i < nrec:
+                            mem[o + 4 * i:o + 4 * i + 4] = vg[l][r0 + i].to_bytes(4, "little")
+                elif op in ("buffer_store_byte", "buffer_store_byte_d16_hi"):
+                    if o < nrec:
+                        mem[o] = (vg[l][r0] >> (16 if op.endswith("hi") else 0)) & 0xFF
+                else:
+                    raise AssertionError(ln)
+    return ex
+
+
+def selfcheck_lens():
+    """The emitted length logic against a byte model: for every bound 0..70 (clamped by the wrapper to
+    the row, as fec_engine.hip packs min(len, blk_len)) on a 64-byte row, and on a 36-byte row whose last
+    16-byte piece is pulled back, the bytes loaded are the row zero-padded with nothing read at or past
+    roundup4(bound), and the bytes stored are exactly blk_len."""
+    rnd = random.Random(3)
+    D0, A0 = 100, 120
+    for VEC in (16, 8, 4):
+        NP = 32 // VEC
+        for cb in (64, 36) if VEC == 16 else (64,):
+            off, ok, active = lanes_model(VEC, cb)
+            live = [l < active for l in range(64)]
+            for want in range(71):
+                n = min(want, cb)
+                row = bytes(rnd.randrange(1, 256) for _ in range(cb + 8))
+                readable = [i < (n + 3) // 4 * 4 for i in range(cb + 8)]
+                sg = {r: rnd.getrandbits(32) for r in range(60, 102)}
+                sg[S_LD], sg[S_LD + 1], sg[S_LD + 3] = 0x1000, 0x7fff | (n << 16), SRD_WORD3
+                sg[S_LEN] = n
+                vg = [{r: rnd.getrandbits(32) for r in range(60, 130)} for _ in range(64)]
+                mem = bytearray(row)
+                lines = lens_loads(VEC, D0) + lens_tail_mask(VEC, D0, "live", "t")
+                ex = simulate_lens(lines, sg, vg, off, ok, live, mem, readable)
+                assert ex == live and mem == row
+                pad = row[:n] + bytes(cb + 8 - n)
+                for l in range(active):
+                    for q in range(NP):
+                        got = b"".join(vg[l][D0 + q * (VEC // 4) + i].to_bytes(4, "little") for i in range(VEC // 4))
+                        o = off[l][q]
+                        assert got == pad[o:o + VEC], (VEC, cb, n, l, q)
+                # store the padded row back as a row of blk_len = n bytes into canaries
+                for l in range(64):
+                    for q in range(NP):
+                        o = off[l][q]
+                        for i in range(VEC // 4):
+                            vg[l][A0 + q * (VEC // 4) + i] = int.from_bytes(row[o + 4 * i:o + 4 * i + 4], "little")
+                sg[S_SD], sg[S_SD + 1], sg[S_SD + 3] = 0x2000, 0x7fff | (n << 16), SRD_WORD3
+                mem = bytearray(b"\xA5" * (cb + 8))
+                ex = simulate_lens(lens_stores(VEC, list(range(A0, A0 + 8)), "live", "t"), sg, vg, off, ok, live,
+                                   mem, [False] * (cb + 8))
+                assert ex == live and mem == row[:n] + b"\xA5" * (cb + 8 - n), (VEC, cb, n)
+
+
+def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False, lens: bool = False):
     """Inline-asm text for one group of blocks x one column chunk.
 
     The sources of all blocks of the group form ONE stream (flattened index s = g*k + j),
     so the P-deep register prefetch runs across block boundaries; when j wraps, the
     per-block epilogue subroutine (reached by s_swappc) transposes the accumulators back,
     stores them and clears them.  mode 'enc' (addresses by stride) or 'dec' (addresses
-    from LDS tables written by the wrapper)."""
+    from LDS tables written by the wrapper).  lens ('dec' only): the length-aware variant, every
+    table entry carries its row's byte bound in bits 48-63 (see the section above lens_loads)."""
     ld, st, nw = LOADOP[VEC]
     NP = 32 // VEC
     DATA_BASE = data_base(mode)
     acc_base = DATA_BASE + 8 * P
     touch = TOUCH if mode == "dec" and EARLY_PF else 0
     epi_pf = mode == "dec" and DEC_EPI_PF and T64
+    assert not lens or (mode == "dec" and EARLY_PF and T64 and not touch and not epi_pf and not sc
+                        and not EXECMASK and INPTR == 67 and NADDR == 70)
     EPI_RT, EPI_AD = PL[0], PL[2]  # v32, v34:35 (planes, dead in the epilogue; clear of t64 scratch)
     assert not epi_pf or (EPI_AD % 2 == 0 and EPI_AD + 1 == PL[3] and {EPI_RT, EPI_AD, EPI_AD + 1}.isdisjoint(
         set(sum(t64_scratch(T_BASE), []))))
@@ -508,6 +741,13 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False):
             a(f"s_cselect_b32 s{S_JL}, 0, s{S_JL}")
         a(f"v_add_u32 v{INPTR}, 8, v{INPTR}")
         a(f"v_mov_b32 v{OUTPTR}, %[outtab]")
+        if lens:  # descriptor word 3, and row 0's bound (the high dword of its table entry)
+            a(f"s_mov_b32 s{S_LD + 3}, 0x{SRD_WORD3:08x}")
+            a(f"s_mov_b32 s{S_SD + 3}, 0x{SRD_WORD3:08x}")
+            a(f"v_readfirstlane_b32 s{S_LENP}, %[intab]")
+            a(f"v_mov_b32 v{LENV}, s{S_LENP}")
+            a(f"ds_read_b32 v{LENV}, v{LENV} offset:4")
+            a(f"s_add_u32 s{S_LENP}, s{S_LENP}, 8")
     # count-down loop counters, tested by the borrow of s_sub_u32 (no compares in the loop):
     # S_S = sources left after this one, S_J = sources left in this block after this one,
     # S_T2 = prefetches left (max(0, nsrc - (P - 1)))
@@ -524,15 +764,18 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False):
             # this source's address was read one source ago (nothing else of the LDS queue is
             # outstanding here but, with EARLY_CO, this step's younger coefficient read, so the
             # wait is free); then fetch the next one
+            cur = S_LD if lens else S_CUR  # lens: the entry is words 0-1 of the load descriptor to be
             out += [f"s_waitcnt lgkmcnt({lgkm})",
-                    f"v_readfirstlane_b32 s{S_CUR}, v{NADDR}",
-                    f"v_readfirstlane_b32 s{S_CUR + 1}, v{NADDR + 1}",
+                    f"v_readfirstlane_b32 s{cur}, v{NADDR}",
+                    f"v_readfirstlane_b32 s{cur + 1}, v{NADDR + 1}",
                     f"ds_read_b64 v[{NADDR}:{NADDR + 1}], v{INPTR}"]
             if touch:  # the touch target read one row ago, and the next one's address
                 out += [f"v_readfirstlane_b32 s{S_O2}, v{TA}",
                         f"v_readfirstlane_b32 s{S_O2 + 1}, v{TA + 1}",
                         f"ds_read_b64 v[{TA}:{TA + 1}], v{INPTR} offset:{8 * (touch - 1)}"]
             out += [f"v_add_u32 v{INPTR}, 8, v{INPTR}"]
+        if lens:
+            return out + lens_loads(VEC, DATA_BASE + 8 * buf)
         # no exec switching: a lane's piece past the chunk end has offset 0 (BsLanes), so its load
         # stays inside the row, and its bytes never reach memory (the stores are masked)
         for q in range(NP):
@@ -573,6 +816,18 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False):
     for b in range(P):
         nb = (b + P - 1) % P
         a(f".Lbody{b}_%=:")
+        if lens:
+            # the bound of the row waiting in buffer b was read a step ago; the next row's goes out now.
+            # lgkmcnt counts in order, so this wait also drains what the 'dec' body leaves in flight across the
+            # step boundary: the address prefetch (NADDR) and, for 16-unknown tiles, the second half of the
+            # coefficient fields (and with EARLY_CO it would drain that read too).  Part of the twin's measured
+            # 2-5 % at equal lengths; a tuning of those reads has to look here first
+            a("s_waitcnt lgkmcnt(0)")
+            a(f"v_readfirstlane_b32 s{S_LEN}, v{LENV}")
+            a(f"v_mov_b32 v{LENV}, s{S_LENP}")
+            a(f"ds_read_b32 v{LENV}, v{LENV} offset:4")
+            a(f"s_add_u32 s{S_LENP}, s{S_LENP}, 8")
+            a(f"s_lshr_b32 s{S_LEN}, s{S_LEN}, 16")
         a(f"s_sub_u32 s{S_T2}, s{S_T2}, 1")
         a(f"s_cbranch_scc1 .Lnopf{b}_%=")
         if EARLY_PF:
@@ -589,7 +844,12 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False):
             if early_co:  # the coefficient fields (into CO = TMP, untouched by transpose64) go out first
                 a(f"{dsr} {regrange(CO[0], ndw)}, v{COPTR}")
                 a(f"v_add_u32 v{COPTR}, {csb}, v{COPTR}")
+            if lens:  # the mask's SALU would lose the borrow that decides the refill below: keep it
+                a(f"s_cselect_b32 s{S_SCC}, 1, 0")
+                L.extend(lens_tail_mask(VEC, DATA_BASE + 8 * b, live, f"b{b}"))
             L.extend(tr[:12])
+            if lens:
+                a(f"s_cmp_lg_u32 s{S_SCC}, 0")
             a(f"s_cbranch_scc1 .Lnold{b}_%=")
             L.extend(load_source(b, 1 if early_co else 0))
             a(f".Lnold{b}_%=:")
@@ -734,6 +994,11 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False):
             a(f"ds_write_b8 v{OUTPTR}, v{TMP[1]} offset:{DEC_REC_NZ + i}")  # non-zero flag (LDS)
             a(f"s_mov_b64 exec, {live}")
             a("s_waitcnt lgkmcnt(0)")
+            if lens:
+                a(f"v_readfirstlane_b32 s{S_SD}, v{TMP[2]}")
+                a(f"v_readfirstlane_b32 s{S_SD + 1}, v{TMP[3]}")
+                L.extend(lens_stores(VEC, accs, live, f"r{i}"))
+                continue
             a(f"v_readfirstlane_b32 s{S_O2}, v{TMP[2]}")
             a(f"v_readfirstlane_b32 s{S_O2 + 1}, v{TMP[3]}")
         for q in range(NP):
@@ -756,6 +1021,10 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False):
     a("s_waitcnt lgkmcnt(0)")
     a(f"s_mov_b64 exec, s[{S_SAVEEX}:{S_SAVEEX + 1}]")
     a(f"s_mov_b32 m0, s{S_SAVEM0}")
+    if lens:  # every row address goes through a descriptor: the plain row pointers are never written or read
+        import re
+        assert not [ln for ln in L if re.search(rf"\bs\[?({S_CUR}|{S_CUR + 1})\b", ln)]
+        assert not [ln for ln in L if ln.startswith("global_")]
     return L, acc_base + 8 * RT + (4 if touch else 0)
 
 
@@ -769,13 +1038,13 @@ def cstring(lines):
     return "\n".join(out)
 
 
-def emit_function(mode, RT, VEC, P, sc=False):
+def emit_function(mode, RT, VEC, P, sc=False, lens=False):
     """sc: the shared-coefficient encode (window blocks, fbn 0): separate per-piece store offsets
     so0.. (a lane's pieces may belong to different windows, whose sources and repairs are laid
-    out with different strides)."""
-    lines, top = body(mode, RT, VEC, P, sc)
+    out with different strides).  lens: the length-aware decode family bs_decl_*."""
+    lines, top = body(mode, RT, VEC, P, sc, lens) if lens else body(mode, RT, VEC, P, sc)
     NP = 32 // VEC
-    name = f"bs_{mode}{'sc' if sc else ''}_r{RT}_v{VEC}"
+    name = f"bs_{mode}{'sc' if sc else ''}{'l' if lens else ''}_r{RT}_v{VEC}"
     offs = ", ".join(f"uint32_t off{q}" for q in range(NP))
     if sc:
         offs += ", " + ", ".join(f"uint32_t so{q}" for q in range(NP))
@@ -794,7 +1063,8 @@ def emit_function(mode, RT, VEC, P, sc=False):
     if sc:
         ins += [f'[so{q}] "v"(so{q})' for q in range(NP)]
     ins += [f'[vm{q}] "s"(vm{q})' for q in range(NP)]
-    clob = [f'"v{r}"' for r in range(T_BASE, top)] + [f'"s{r}"' for r in SGPR_CLOBBER] + ['"vcc"', '"scc"', '"memory"']
+    sclob = SGPR_CLOBBER + (SGPR_CLOBBER_LENS if lens else [])
+    clob = [f'"v{r}"' for r in range(T_BASE, top)] + [f'"s{r}"' for r in sclob] + ['"vcc"', '"scc"', '"memory"']
     out = [sig + " {", "  asm volatile(", cstring(lines), "      :",
            "      : " + ", ".join(ins), "      : " + ", ".join(clob) + ");", "}"]
     return "\n".join(out), top
@@ -1445,5 +1715,48 @@ def main():
     print(f"wrote {OUT}: {len(CONFIGS) * 2} + 4 + {4 * len(tiles2)} bodies, max VGPR {max(tops.values())}")
 
 
+def main_lens():
+    """bitslice_lens_gen.h: the length-aware decode bodies (rows of their own length,
+    fecgpu_rlc_*_rows_fused), one for every tile and piece size."""
+    selfcheck_t64()
+    selfcheck_lens()
+    parts = ["// GENERATED by pquic_amd/csrc/gen_bitslice.py -- do not edit.",
+             "// Length-aware decode bodies bs_decl_* (see the generator, 'rows of their own length'); included",
+             "// after bitslice_gen.h, whose macros and case table they use.",
+             "#pragma once",
+             "#include <hip/hip_runtime.h>",
+             "#include <stdint.h>",
+             ""]
+    tops = {}
+    for RT, VEC in CONFIGS:
+        # 8 unknowns x 4-byte pieces (symbols of 4 or 12 bytes) sit at the 168-VGPR edge of 3 waves/SIMD with 8
+        # lane offsets live across the body: the recover kernel's length setup took one register more and fell
+        # to 2 waves, so this body gives up one row in flight
+        P = prefetch_depth("dec", RT, VEC) - (1 if (RT, VEC) == (8, 4) else 0)
+        fn, top = emit_function("dec", RT, VEC, P, lens=True)
+        tops[("decl", RT, VEC, P)] = top
+        parts.append(fn)
+        parts.append("")
+    tmp = OUT_LENS + ".tmp"  # whole or not at all: a build may be interrupted
+    with open(tmp, "w") as f:
+        f.write("\n".join(parts))
+    os.replace(tmp, OUT_LENS)
+    print(f"wrote {OUT_LENS}: {len(CONFIGS)} bodies, max VGPR {max(tops.values())}")
+
+
 if __name__ == "__main__":
-    main()
+    import subprocess
+    import sys
+    variant = sorted(k for k in os.environ if k.startswith("FEC_GEN") and k != "FEC_GEN_OUT")
+    if "--lens-only" in sys.argv:
+        main_lens()
+    elif variant:
+        # an A/B variant of the equal-length bodies (tools/gen_variant.py, build_gen_variant.py): the length-aware
+        # family has no variants (body() asserts the settings it was written for), so it is generated with the
+        # defaults, beside the variant's header, as pquic_amd/build.py does
+        main()
+        env = {k: v for k, v in os.environ.items() if k not in variant}
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--lens-only"], env=env, check=True)
+    else:
+        main()
+        main_lens()

@@ -4,7 +4,7 @@
 // receive, sender.c:1084 on send).  These entry points move a batch of FEC blocks through
 // the device: per sub-batch, H2D copy -> fecgpu_* kernels -> D2H copy on one of `nstreams`
 // streams, so the copies of one sub-batch overlap the kernels of the next.
-// The table forms (*_rows_host, *_rows_len_host) take rows by device address and copy no payload: their
+// The table forms (*_rows_host, *_rows_len_host, *_rows_fused_host) take rows by device address and copy no payload: their
 // per-block arrays go through stage_tables() / unstage_tables(), their launches through for_slices().
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -710,6 +710,67 @@ int fecgpu_rlc_decode_rows_len_host(fecgpu_host_ctx_t *c, const uint64_t *src_ro
           t[RLEN].at<const uint32_t>(b0), t[BLEN].at<const uint32_t>(b0), m, k, r, L, t[SEED].at<const uint32_t>(b0),
           t[SP].at<const uint64_t>(b0), t[RP].at<const uint64_t>(b0), t[ST].at<uint8_t>(b0), t[REC].at<uint64_t>(b0),
           w.d_src, w.d_rep, (uint8_t *)w.d_rep + o_rec, w.d_ws, w.cap_ws, w.st);
+    });
+  return finish(c, unstage_tables(c, t, nblocks, in_place, rc));
+}
+
+// ---- ragged rows in one pass (fecgpu_rlc_encode_rows_fused_host / fecgpu_rlc_decode_rows_fused_host) ----
+// No packed arrays: a sub-batch needs its slot's stream, and decode its plan workspace.
+int fecgpu_rlc_encode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                      const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nblocks,
+                                      uint32_t k, uint32_t r, uint32_t L, const uint32_t *fbn) {
+  if (!src_rows || !src_len || !rep_rows || !blk_len) return rows_len_invalid("NULL row / length table");
+  if (int rc = rows_len_shape(k, r, L)) return rc;
+  if (int rc = rows_len_check(src_len, blk_len, nullptr, nblocks, k, L)) return rc;
+  if (!c) return rows_len_invalid("NULL host context");
+  if (!nblocks || !r) return FECGPU_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HCHK(hipSetDevice(c->device));
+  enum { SRC, REP, SLEN, BLEN, FBN };
+  Table t[] = {in(src_rows, k * 8), in(rep_rows, r * 8), in(src_len, k * 4), in(blk_len, 4), in(fbn, fbn ? 4 : 0)};
+  bool in_place;
+  int rc = stage_tables(c, t, nblocks, &in_place);
+  const size_t bb = (size_t)(k + r) * L;
+  if (!rc)
+    rc = for_slices(c, nblocks, bb, sub_batch(c, nblocks, bb), in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
+      // without fbn[] block b is block number b (fecgpu.h:21): sub-batch b0 starts at b0, not 0
+      return fecgpu_rlc_encode_rows_fused(t[SRC].at<const uint64_t>(b0), t[SLEN].at<const uint32_t>(b0),
+                                          t[REP].at<const uint64_t>(b0), t[BLEN].at<const uint32_t>(b0), m, k, r, L,
+                                          fbn ? 0u : (uint32_t)(b0 & 0xffffffu),
+                                          fbn ? t[FBN].at<const uint32_t>(b0) : nullptr, w.st);
+    });
+  return finish(c, rc);
+}
+
+int fecgpu_rlc_decode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                      const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                      uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
+                                      const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+  if (!src_rows || !src_len || !blk_len || (r && (!rep_rows || !rep_len || !seeds)))
+    return rows_len_invalid("NULL row / length table");
+  if (!sp || !rp || !status || !recovered) return rows_len_invalid("NULL mask/status");
+  if (int rc = rows_len_shape(k, r, L)) return rc;
+  if (int rc = rows_len_check(src_len, blk_len, sp, nblocks, k, L)) return rc;
+  if (!c) return rows_len_invalid("NULL host context");
+  if (!nblocks) return FECGPU_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HCHK(hipSetDevice(c->device));
+  enum { SRC, SLEN, BLEN, REP, RLEN, SEED, SP, RP, ST, REC };
+  Table t[] = {in(src_rows, k * 8), in(src_len, k * 4), in(blk_len, 4), in(rep_rows, r * 8), in(rep_len, r * 4),
+               in(seeds, r * 4),    in(sp, 16),         in(rp, 16),     out(status, 1),      out(recovered, 16)};
+  bool in_place;
+  int rc = stage_tables(c, t, nblocks, &in_place);
+  const size_t bb = (size_t)(k + r) * L;
+  if (!rc)
+    rc = for_slices(c, nblocks, bb, sub_batch(c, nblocks, bb), in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
+      HCHK(grow(&w.d_ws, &w.cap_ws, fecgpu_rlc_decode_workspace(m, k, r)));
+      // with r == 0 the repair tables have no entries; the device form wants non-NULL ones
+      return fecgpu_rlc_decode_rows_fused(
+          t[SRC].at<const uint64_t>(b0), t[SLEN].at<const uint32_t>(b0),
+          r ? t[REP].at<const uint64_t>(b0) : t[SRC].at<const uint64_t>(b0),
+          r ? t[RLEN].at<const uint32_t>(b0) : t[SLEN].at<const uint32_t>(b0), t[BLEN].at<const uint32_t>(b0), m, k, r,
+          L, t[SEED].at<const uint32_t>(b0), t[SP].at<const uint64_t>(b0), t[RP].at<const uint64_t>(b0),
+          t[ST].at<uint8_t>(b0), t[REC].at<uint64_t>(b0), w.d_ws, w.cap_ws, w.st);
     });
   return finish(c, unstage_tables(c, t, nblocks, in_place, rc));
 }

@@ -109,6 +109,11 @@ def load_library(path: str = LIB_PATH, private: bool = False):
         L.fecgpu_rlc_decode_rows_len.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v, v, sz, v]
         L.fecgpu_rlc_encode_rows_len_host.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v]
         L.fecgpu_rlc_decode_rows_len_host.argtypes = [v, v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v]
+    if hasattr(L, "fecgpu_rlc_encode_rows_fused"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
+        L.fecgpu_rlc_encode_rows_fused.argtypes = [v, v, v, v, u64, u32, u32, u32, u32, v, v]
+        L.fecgpu_rlc_decode_rows_fused.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v, v, sz, v]
+        L.fecgpu_rlc_encode_rows_fused_host.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v]
+        L.fecgpu_rlc_decode_rows_fused_host.argtypes = [v, v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v]
     if hasattr(L, "fecgpu_xor_encode_rows"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
         L.fecgpu_xor_encode_rows.argtypes = [v, v, v, v, u64, u32, u32, v]
         L.fecgpu_xor_decode_rows.argtypes = [v, v, v, v, u64, u32, u32, v, v, v, v, v]
@@ -395,6 +400,27 @@ class Engine:
             _addr(workspace), workspace.numel(), self._stream(stream)), "fecgpu_rlc_decode_rows_len")
         return status, recovered
 
+    def rlc_encode_rows_fused(self, src_rows, src_len, rep_rows, blk_len, nblocks: int, k: int, r: int, L: int,
+                              fbn_base: int = 0, fbn=None, stream=None):
+        """fecgpu_rlc_encode_rows_fused: ragged rows in one pass, no workspace; every repair row receives
+        exactly blk_len[b] bytes."""
+        self._check(self.lib.fecgpu_rlc_encode_rows_fused(
+            _addr(src_rows), _addr(src_len), _addr(rep_rows), _addr(blk_len), nblocks, k, r, L, fbn_base,
+            _addr(fbn), self._stream(stream)), "fecgpu_rlc_encode_rows_fused")
+
+    def rlc_decode_rows_fused(self, src_rows, src_len, rep_rows, rep_len, blk_len, rep_seed, src_present,
+                              rep_present, status, recovered, nblocks: int, k: int, r: int, L: int,
+                              workspace=None, stream=None):
+        """fecgpu_rlc_decode_rows_fused: ragged rows in one pass, per-repair seeds; the workspace is the plan's
+        (decode_workspace_bytes).  Every missing source whose recovered bit is set holds its blk_len[b] bytes."""
+        if workspace is None:
+            workspace = self.alloc_workspace(nblocks, k, r)
+        self._check(self.lib.fecgpu_rlc_decode_rows_fused(
+            _addr(src_rows), _addr(src_len), _addr(rep_rows), _addr(rep_len), _addr(blk_len), nblocks, k, r, L,
+            _addr(rep_seed), _addr(src_present), _addr(rep_present), _addr(status), _addr(recovered),
+            _addr(workspace), workspace.numel(), self._stream(stream)), "fecgpu_rlc_decode_rows_fused")
+        return status, recovered
+
     def xor_encode_rows(self, src_rows, src_len, rep_rows, blk_len, nblocks: int, k: int, L: int, stream=None):
         """fecgpu_xor_encode_rows: one pass over rows given by address (u64 tables) and length (u32);
         rep_rows[b] receives exactly blk_len[b] bytes."""
@@ -477,6 +503,21 @@ class HostPath:
                                                            nblocks, k, r, L, _addr(seeds), _addr(sp), _addr(rp),
                                                            _addr(status), _addr(rec)),
                   "fecgpu_rlc_decode_rows_len_host")
+
+    def rlc_encode_rows_fused(self, src_rows, src_len, rep_rows, blk_len, nblocks, k, r, L, fbn=None):
+        """fecgpu_rlc_encode_rows_fused_host: host tables and lengths; the rows must be device-accessible."""
+        self._chk(self.lib.fecgpu_rlc_encode_rows_fused_host(self.ctx, _addr(src_rows), _addr(src_len),
+                                                             _addr(rep_rows), _addr(blk_len), nblocks, k, r, L,
+                                                             _addr(fbn)), "fecgpu_rlc_encode_rows_fused_host")
+
+    def rlc_decode_rows_fused(self, src_rows, src_len, rep_rows, rep_len, blk_len, seeds, sp, rp, status, rec,
+                              nblocks, k, r, L):
+        """fecgpu_rlc_decode_rows_fused_host: host tables, lengths, seeds, masks, status and recovered."""
+        self._chk(self.lib.fecgpu_rlc_decode_rows_fused_host(self.ctx, _addr(src_rows), _addr(src_len),
+                                                             _addr(rep_rows), _addr(rep_len), _addr(blk_len),
+                                                             nblocks, k, r, L, _addr(seeds), _addr(sp), _addr(rp),
+                                                             _addr(status), _addr(rec)),
+                  "fecgpu_rlc_decode_rows_fused_host")
 
     def xor_encode_rows(self, src_rows, src_len, rep_rows, blk_len, nblocks, k, L):
         """fecgpu_xor_encode_rows_host: host tables and lengths; the rows must be device-accessible."""

@@ -16,4 +16,6 @@ os.makedirs(vdir, exist_ok=True)
 hdr = os.path.join(vdir, "bitslice_gen.h")
 env = dict(os.environ, FEC_GEN_OUT=hdr, **dict(s.split("=", 1) for s in sets))
 subprocess.run([sys.executable, os.path.join(B.CSRC, "gen_bitslice.py")], env=env, check=True)
-B.build(verbose=True, out=os.path.join(vdir, "libpquic_fec.so"), defines=[f'FEC_GEN_HDR="{hdr}"'])
+lens = os.path.join(vdir, "bitslice_lens_gen.h")  # the generator writes it beside FEC_GEN_OUT
+B.build(verbose=True, out=os.path.join(vdir, "libpquic_fec.so"),
+        defines=[f'FEC_GEN_HDR="{hdr}"', f'FEC_GEN_LENS_HDR="{lens}"'])

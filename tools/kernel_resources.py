@@ -6,6 +6,10 @@ import subprocess
 import sys
 
 ROOT = __file__.rsplit("/tools/", 1)[0]
+sys.path.insert(0, ROOT)
+from pquic_amd import build as B  # noqa: E402
+
+B.generate_lens_header()  # fec_engine.hip includes the build-generated bitslice_lens_gen.h
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c",
        f"{ROOT}/pquic_amd/csrc/fec_engine.hip", "-o", "/dev/null", f"-I{ROOT}/include", f"-I{ROOT}/pquic_amd/csrc",
        "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:]

@@ -4,7 +4,9 @@
            against fecgpu_rlc_encode_rows / fecgpu_rlc_decode_rows on the same device-resident rows: k16 r4
            L1200 at 2^16 blocks and k64 r16 L9000 at 2^12 blocks, interleaved, timed with events.  The
            _len forms move every row through device memory twice more (gather, scatter): the ratio is
-           their price, recorded so nobody calls them free.
+           their price, recorded so nobody calls them free.  The one-pass forms (fecgpu_rlc_*_rows_fused) run
+           beside them, and a second pass repeats all six on ragged rows (the lengths of `copies`, the block
+           as long as its longest source): the figures of profiles/rows_fused.log.
   copies   the gather and scatter kernels alone on the k16 r4 L1200 rows (device memory and page-locked
            host memory): the A/B behind their launch shape, one line per library build
            (PQUIC_AMD_LIB selects a build with another -DFEC_ROWS_LPR).
@@ -104,23 +106,41 @@ def mode_device():
                                                 dws.data_ptr(), dws.numel(), stream)
             assert rc == 0, eng.err()
 
-        fns = {
-            "encode_rows": lambda: eng.rlc_encode_rows(srow, rrow, nb, k, r, L),
-            "encode_rows_len": lambda: eng.rlc_encode_rows_len(srow, slen, rrow, blen, nb, k, r, L, workspace=ws),
-            "decode_rows": dec_rows,
-            "decode_rows_len": lambda: eng.rlc_decode_rows_len(srow, slen, rrow, rlen, blen, seeds, sp, rp, st, rec,
-                                                              nb, k, r, L, workspace=ws),
-        }
-        fns["encode_rows_len"]()
-        torch.cuda.synchronize()
-        assert torch.equal(rep, keep), "encode_rows_len differs from encode_rows"
-        t = timed(fns, args.repeats)
-        payload = nb * k * L
-        print(f"k{k} r{r} e{e} L{L}, {nb} blocks, device-resident rows, {args.repeats} interleaved repeats")
-        for n, xs in t.items():
-            print(f"  {n:16s} {med_range(xs)}  {payload / statistics.median(xs) / 1073.741824:8.1f} GiB/s payload")
-        for a, b in (("encode_rows_len", "encode_rows"), ("decode_rows_len", "decode_rows")):
-            print(f"  {a} / {b}: x{statistics.median(t[a]) / statistics.median(t[b]):.2f}", flush=True)
+        fused = hasattr(eng.lib, "fecgpu_rlc_encode_rows_fused")  # an older build (PQUIC_AMD_LIB) lacks the legs
+        rag_s = torch.randint(40, L + 1, (nb * k,), generator=torch.Generator().manual_seed(7)).to(torch.int32).to(dev)
+        rag_b = rag_s.reshape(nb, k).max(1).values.contiguous()
+        rag_r = rag_b.repeat_interleave(r).contiguous()
+        for what, sl, rl, bl in (("equal lengths", slen, rlen, blen), ("ragged lengths", rag_s, rag_r, rag_b)):
+            fns = {
+                "encode_rows": lambda: eng.rlc_encode_rows(srow, rrow, nb, k, r, L),
+                "encode_rows_len": lambda: eng.rlc_encode_rows_len(srow, sl, rrow, bl, nb, k, r, L, workspace=ws),
+                "decode_rows": dec_rows,
+                "decode_rows_len": lambda: eng.rlc_decode_rows_len(srow, sl, rrow, rl, bl, seeds, sp, rp, st, rec,
+                                                                  nb, k, r, L, workspace=ws),
+            }
+            if fused:
+                fns["encode_rows_fused"] = lambda: eng.rlc_encode_rows_fused(srow, sl, rrow, bl, nb, k, r, L)
+                fns["decode_rows_fused"] = lambda: eng.rlc_decode_rows_fused(srow, sl, rrow, rl, bl, seeds, sp, rp, st,
+                                                                            rec, nb, k, r, L, workspace=dws)
+            if sl is slen:
+                for n in ("encode_rows_len", "encode_rows_fused") if fused else ("encode_rows_len",):
+                    rep.zero_()
+                    fns[n]()
+                    torch.cuda.synchronize()
+                    assert torch.equal(rep, keep), f"{n} differs from encode_rows"
+            t = timed(fns, args.repeats)
+            payload = int(sl.sum())
+            print(f"k{k} r{r} e{e} L{L}, {nb} blocks, device-resident rows, {what}, {args.repeats} interleaved repeats")
+            for n, xs in t.items():
+                print(f"  {n:18s} {med_range(xs)}  {payload / statistics.median(xs) / 1073.741824:8.1f} GiB/s payload")
+            for a, b in (("encode_rows_len", "encode_rows"), ("decode_rows_len", "decode_rows")):
+                print(f"  {a} / {b}: x{statistics.median(t[a]) / statistics.median(t[b]):.2f}", flush=True)
+            if fused:
+                for a in ("encode", "decode"):
+                    f, ln, eq = t[a + "_rows_fused"], t[a + "_rows_len"], t[a + "_rows"]
+                    print(f"  {a}_rows_fused / {a}_rows: x{statistics.median(f) / statistics.median(eq):.2f}; "
+                          f"fused median {statistics.median(f):.1f} us against the minimum of {a}_rows_len "
+                          f"{min(ln):.1f} us: {'below' if statistics.median(f) < min(ln) else 'NOT below'}", flush=True)
         del src, rep, ws, dws, keep
         torch.cuda.empty_cache()
 
