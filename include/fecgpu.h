@@ -107,6 +107,17 @@ int fecgpu_rlc_decode_rows(const uint64_t *src_rows, const uint64_t *rep_rows, u
                            const uint64_t *rep_present, uint8_t *status, uint64_t *recovered, void *workspace,
                            size_t workspace_bytes, void *stream);
 
+/* fecgpu_rlc_decode_rows in full-rank mode: status, recovered and the recovered bytes are those of
+ * fecgpu_rlc_decode_full with rep_seed on the packed rows (RECOVERED whenever the received repairs
+ * determine the block, SINGULAR otherwise, never REF_UB).  Row rules are fecgpu_rlc_decode_rows's, and one
+ * more: a present repair that full mode does not select (it is dependent on earlier ones, or past the
+ * n-th independent one) is never dereferenced, like an absent one -- its address may be 0.  A SINGULAR
+ * block reads and writes no row. */
+int fecgpu_rlc_decode_rows_full(const uint64_t *src_rows, const uint64_t *rep_rows, uint64_t nblocks, uint32_t k,
+                                uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Ragged rows: symbols of their own length, coded where they lie ------------------------------
  * The reference codes symbols of different lengths: generate reads every source for its own
  * data_length and allocates repairs of the block's max_length (rlc_fec_scheme_generate_gf256.c:41-66);
@@ -188,6 +199,15 @@ int fecgpu_rlc_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_l
                                  uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
                                  const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
                                  uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream);
+/* fecgpu_rlc_decode_rows_fused in full-rank mode: status[] and recovered[] are what fecgpu_rlc_decode_full
+ * with rep_seed gives on the zero-padded rows; lengths, clamping and address rules as above.  A repair
+ * full mode does not select is never dereferenced; a SINGULAR block reads and writes no row.  (The
+ * *_rows_len forms have no full-rank counterpart.) */
+int fecgpu_rlc_decode_rows_fused_full(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                      const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                      uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                      const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                      uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream);
 
 /* XOR encode (r == 1): rep[b][0] = XOR_j src[b][j]. */
 int fecgpu_xor_encode(const void *src, void *rep, uint64_t nblocks, uint32_t k,
@@ -307,7 +327,10 @@ int fecgpu_rlc_decode_seeded(void *src, const void *rep, uint64_t nblocks, uint3
  * (fbn_b << 8) | i as in fecgpu_rlc_decode.  Workspace, masks, status and recovered as fecgpu_rlc_decode.
  * fecgpu_rlc_decode_plan_full writes the same plan records as fecgpu_rlc_decode_plan (the reference plan,
  * then a fix-up pass that re-plans the blocks it gave up on) and pairs with fecgpu_rlc_decode_apply,
- * _apply_to and _apply_packed; fecgpu_rlc_decode_full is plan_full + apply, always as separate launches. */
+ * _apply_to and _apply_packed; fecgpu_rlc_decode_full is plan_full + apply as separate launches, except that
+ * a batch of up to 64 blocks with at most 16 unknowns each whose rows fit a workgroup's LDS is one launch (the
+ * one-block kernel re-plans a given-up block in place); knob plan != 0 forces the separate launches.  The
+ * outputs are the same either way. */
 int fecgpu_rlc_decode_plan_full(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t fbn_base, const uint32_t *fbn,
                                 const uint32_t *rep_seed, const uint64_t *src_present, const uint64_t *rep_present,
                                 void *workspace, size_t workspace_bytes, void *stream);
@@ -369,6 +392,11 @@ int fecgpu_rlc_decode_rows_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows
                                 uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
                                 const uint32_t *rep_seed, const uint64_t *src_present, const uint64_t *rep_present,
                                 uint8_t *status, uint64_t *recovered);
+/* the same in full-rank mode (fecgpu_rlc_decode_rows_full): same staging, same slices */
+int fecgpu_rlc_decode_rows_host_full(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint64_t *rep_rows,
+                                     uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
+                                     const uint32_t *rep_seed, const uint64_t *src_present,
+                                     const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
 /* fecgpu_rlc_encode_rows_len / fecgpu_rlc_decode_rows_len from the host: the row tables, length tables,
  * fbn[] / seeds, masks, status and recovered are host arrays (page-locked ones are used in place,
  * others are copied); the rows must be device-accessible.  The batch runs in sub-batches of about
@@ -395,6 +423,12 @@ int fecgpu_rlc_decode_rows_fused_host(fecgpu_host_ctx_t *ctx, const uint64_t *sr
                                       uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
                                       const uint32_t *rep_seed, const uint64_t *src_present,
                                       const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
+/* fecgpu_rlc_decode_rows_fused_host in full-rank mode (fecgpu_rlc_decode_rows_fused_full) */
+int fecgpu_rlc_decode_rows_fused_host_full(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint32_t *src_len,
+                                           const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                           uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
+                                           const uint32_t *rep_seed, const uint64_t *src_present,
+                                           const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
 /* fecgpu_rlc_window_encode_table from the host: the stream (host rows) crosses PCIe once, by one copy,
  * before the windows are coded from device memory -- a symbol serves up to k windows, so reading it in
  * place would cross the bus that many times; wrow[] is a host array; repairs go to page-locked `rep` in
@@ -442,6 +476,16 @@ int fecgpu_block_svc_rlc_decode_seeded(fecgpu_block_svc_t *svc, const void *src,
                                        uint32_t k, uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
                                        const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
                                        uint64_t *recovered);
+/* The same in full-rank mode (fecgpu_rlc_decode_full with rep_seed, one block): the worker re-plans a
+ * block the reference elimination gives up on from every received repair, inside the same request, so
+ * status is RECOVERED or SINGULAR where the call above reports REF_UB.  The mode belongs to the request,
+ * not to the service: calls of both kinds may alternate on one service.  Arguments and the page-lock
+ * check are the call's above; the re-plan's scratch counts against the worker's LDS, so a few large
+ * blocks the call above takes are refused here (FECGPU_ERR_INVALID: take fecgpu_rlc_decode_host_full). */
+int fecgpu_block_svc_rlc_decode_full(fecgpu_block_svc_t *svc, const void *src, const void *rep, void *dst,
+                                     uint32_t k, uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                     const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                     uint64_t *recovered);
 /* worker generations launched so far (diagnostics: one per idle gap) */
 uint64_t fecgpu_block_svc_launches(const fecgpu_block_svc_t *svc);
 /* A call waits at most `deadline_us` (default 2000) for a worker to take its request.  Past it the

@@ -67,12 +67,14 @@ typedef struct {
 } pquic_fec_batch_stats_t;
 
 /* NULL on failure (bad configuration, no device, out of pinned memory).
- * The adapter reads three environment variables, once per batcher, here (a value below the minimum
+ * The adapter reads four environment variables, once per batcher, here (a value below the minimum
  * counts as unset, one above the maximum as the maximum):
  *   PQUIC_FEC_BATCH_STAGERS   copy threads, 1..16; default half the CPUs of the process's share, at least 2
  *   PQUIC_FEC_BATCH_ENGINES   engine threads, each with its own host context and streams, 1..4; default 2
  *   PQUIC_FEC_BATCH_PREFETCH  blocks ahead a completion prefetches the symbols it hands over, 0..64
- *                             (0: off); default 8 */
+ *                             (0: off); default 8
+ *   PQUIC_FEC_BATCH_FULL_RANK 0 or 1: the batcher starts in full-rank mode (pquic_fec_batch_set_full_rank);
+ *                             default 0; ignored against an engine library without the full-rank entry points */
 pquic_fec_batcher_t *pquic_fec_batcher_create(const pquic_fec_batch_cfg_t *cfg);
 /* Drains (completing every queued block) and frees. */
 void pquic_fec_batcher_destroy(pquic_fec_batcher_t *b);
@@ -125,6 +127,17 @@ int pquic_fec_batch_generate_window(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx,
 /* Queue fec_recover for `fb` (the receiver's block copy, fec_protoops.h:220-222). */
 int pquic_fec_batch_recover(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t *fb, int xor_scheme,
                             uint64_t now_us, pquic_fec_block_done_fn done, void *user);
+
+/* Full-rank recovery for the RLC recover jobs of this batcher (on != 0; 0: the reference's elimination, the
+ * default).  A full-rank job recovers every block its received repairs determine -- also where the reference
+ * gives up on a zero pivot, and through repairs past the first n -- by fecgpu_rlc_decode_rows_fused_host_full
+ * (ragged blocks in place), fecgpu_rlc_decode_rows_host_full (whole blocks in place) or
+ * fecgpu_rlc_decode_host_full (staged); a block they do not determine completes with nothing recovered and
+ * is counted by pquic_fec_singular_blocks().  Pre-allocation at submission, the order in which unrecovered
+ * pre-allocations are freed, completion order and FPIDs are the same in both modes; generate and XOR jobs
+ * are not affected.  Call from the submitting thread.  Returns 0, or -1 while any block is queued or in
+ * flight (drain first) and against an engine library without the three entry points. */
+int pquic_fec_batch_set_full_rank(pquic_fec_batcher_t *b, int on);
 
 /* Flushes every queue that is full or past its deadline at `now_us`, then runs `done` for
  * the blocks whose batch has finished: all of them, or at most cfg.poll_blocks.  Batches complete

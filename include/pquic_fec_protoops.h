@@ -108,6 +108,22 @@ protoop_arg_t pquic_fec_xor_create_fec_schemes(picoquic_cnx_t *cnx);
 protoop_arg_t pquic_fec_xor_generate_repair_symbols(picoquic_cnx_t *cnx);
 protoop_arg_t pquic_fec_xor_recover(picoquic_cnx_t *cnx);
 
+/* How pquic_fec_rlc_recover solves a block.  0 (default): the reference's elimination, bit for bit -- the
+ * first n received repairs, one sort, no re-pivoting; a block it gives up on (a zero pivot, where the
+ * reference reads out of bounds) returns 0 with nothing inserted and counts in ref_ub_blocks.  1: full
+ * rank -- every block the received repairs determine is recovered, through a later repair where the first
+ * n are dependent; the recovered symbols have the reference's FPIDs and lengths, so the frameworks see no
+ * difference but more recovered symbols.  A block they do not determine returns what a given-up block
+ * returns in mode 0, inserts nothing and counts in pquic_fec_singular_blocks(); ref_ub_blocks stays 0.
+ * XOR is not affected.  Process-wide, like pquic_fec_bind_host; takes effect from the next call.
+ * Returns 0, or -1 for any other value, and for mode 1 against an engine library without the full-rank
+ * entry points (the mode then stays as it was). */
+int pquic_fec_set_recover_mode(int mode);
+int pquic_fec_get_recover_mode(void);
+/* Blocks full-rank recovery found undetermined so far, in the protocol operations and in the batching
+ * adapter's completions alike. */
+uint64_t pquic_fec_singular_blocks(void);
+
 /* packet_payload_to_source_symbol (protoops/packet_payload_to_source_symbol.c:6-36, manifest
  * fec_core.plugin:20): inputs [0] payload bytes, [1] symbol buffer, [2] payload length,
  * [3] packet number; returns the symbol length, PQUIC_ERROR_MEMORY for a NULL buffer, or

@@ -71,6 +71,14 @@ static int rows_len_available(void) {
 static int rows_fused_available(void) {
     return fecgpu_rlc_encode_rows_fused_host != NULL && fecgpu_rlc_decode_rows_fused_host != NULL;
 }
+/* And full-rank recovery (pquic_fec_batch_set_full_rank): one entry point per way a recover job runs. */
+#pragma weak fecgpu_rlc_decode_host_full
+#pragma weak fecgpu_rlc_decode_rows_host_full
+#pragma weak fecgpu_rlc_decode_rows_fused_host_full
+static int full_rank_available(void) {
+    return fecgpu_rlc_decode_host_full != NULL && fecgpu_rlc_decode_rows_host_full != NULL &&
+           fecgpu_rlc_decode_rows_fused_host_full != NULL;
+}
 static int xor_rows_available(void) {
     return fecgpu_xor_encode_rows_host != NULL && fecgpu_xor_decode_rows_host != NULL;
 }
@@ -135,6 +143,7 @@ typedef struct job {
     uint32_t *order;               /* window: [cap] entries grouped by connection */
     size_t rowsym_cap;
     uint64_t nrows;                /* window: stream rows */
+    int full;                      /* RLC recover: full-rank mode, the batcher's when the job was flushed */
 } job_t;
 
 struct pquic_fec_batcher {
@@ -153,6 +162,7 @@ struct pquic_fec_batcher {
     job_t *todo_head, *todo_tail, *staged_head, *staged_tail, *post_head, *post_tail, *done_head, *done_tail;
     int inflight, stop, stagers_done;
     uint32_t pf;                   /* completion prefetch distance in blocks (prefetch_syms; 0: off) */
+    int full_rank;                 /* caller thread: RLC recover jobs run in full-rank mode (set_full_rank) */
     int done_ready;                /* atomic: the next job in flush order is finished (set under mu), so a
                                     * poll with nothing to complete takes no lock */
     uint64_t next_due;             /* caller thread: the oldest first-submission time of the open jobs
@@ -518,6 +528,15 @@ static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
                                             j->rec);
     else if (j->gather && j->xor_scheme)
         j->rc = fecgpu_xor_encode_rows_host(c, j->srow, j->slen, j->rrow, j->blen, j->n, j->k, S);
+    else if (j->full && j->gather && j->ragged)  /* full rank: the same three ways, through the *_full forms */
+        j->rc = fecgpu_rlc_decode_rows_fused_host_full(c, j->srow, j->slen, j->rrow, j->rlen, j->blen, j->n, j->k,
+                                                       j->r, S, j->seeds, j->sp, j->rp, j->st, j->rec);
+    else if (j->full && j->gather)
+        j->rc = fecgpu_rlc_decode_rows_host_full(c, j->srow, j->rrow, j->n, j->k, j->r, S, j->seeds, j->sp, j->rp,
+                                                 j->st, j->rec);
+    else if (j->full)
+        j->rc = fecgpu_rlc_decode_host_full(c, j->src, j->rep, j->n, j->k, j->r, S, 0, NULL, j->seeds, j->sp, j->rp,
+                                            j->st, j->rec);
     else if (j->gather && j->ragged && rows_fused_available() && j->op == OP_RECOVER)
         j->rc = fecgpu_rlc_decode_rows_fused_host(c, j->srow, j->slen, j->rrow, j->rlen, j->blen, j->n, j->k, j->r, S,
                                                   j->seeds, j->sp, j->rp, j->st, j->rec);
@@ -1009,7 +1028,7 @@ static void *worker_main(void *arg) {
     return NULL;
 }
 
-/* The adapter's three environment settings (pquic_fec_batch.h), read once per batcher: the variable's
+/* The adapter's environment settings (pquic_fec_batch.h), read once per batcher: the variable's
  * value, at most `max`; `def` when it is unset or below `min`. */
 static int env_int(const char *name, int def, int min, int max) {
     const char *s = getenv(name);
@@ -1026,6 +1045,7 @@ pquic_fec_batcher_t *pquic_fec_batcher_create(const pquic_fec_batch_cfg_t *cfg) 
     b->stride = fec_pad4(cfg->max_symbol);
     b->next_due = UINT64_MAX;
     b->pf = (uint32_t)env_int("PQUIC_FEC_BATCH_PREFETCH", 8, 0, 64);
+    b->full_rank = env_int("PQUIC_FEC_BATCH_FULL_RANK", 0, 0, 1) && full_rank_available();
     const size_t chunk = (size_t)cfg->batch_blocks * 20 * b->stride / (size_t)cfg->nstreams;
     b->nengines = env_int("PQUIC_FEC_BATCH_ENGINES", 2, 1, MAX_ENGINES);
     for (int e = 0; e < b->nengines; e++) {
@@ -1101,6 +1121,7 @@ static void flush_job(pquic_fec_batcher_t *b, int slot, uint64_t *counter) {
     }
     (*counter)++;
     b->stats.batches++;
+    j->full = b->full_rank && j->op == OP_RECOVER && !j->xor_scheme;
     j->seq = b->next_seq++;
     pthread_mutex_lock(&b->mu);
     j->next = NULL;
@@ -1413,6 +1434,13 @@ static int deadline_pass(pquic_fec_batcher_t *b, uint64_t now_us) {
     }
     b->stats.deadline_holds += (uint64_t)held;
     return held;
+}
+
+int pquic_fec_batch_set_full_rank(pquic_fec_batcher_t *b, int on) {
+    if (!b || !full_rank_available()) return -1;
+    if (b->stats.submitted != b->stats.completed) return -1;  /* a block is queued or in flight */
+    b->full_rank = on != 0;
+    return 0;
 }
 
 int pquic_fec_batch_poll(pquic_fec_batcher_t *b, uint64_t now_us) {

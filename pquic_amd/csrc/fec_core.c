@@ -150,6 +150,7 @@ protoop_arg_t fec_recover_finish(picoquic_cnx_t *cnx, pquic_fec_block_t *fb, int
                                  uint64_t *nrec_acc) {
     const int k = fb->total_source_symbols;
     if (status == FECGPU_BLOCK_REF_UB) FEC_STAT_ADD(ref_ub_blocks, 1);
+    if (status == FECGPU_BLOCK_SINGULAR) __atomic_fetch_add(&g_fec_singular_blocks, 1, __ATOMIC_RELAXED);
     if (!xor_scheme) {
         const uint32_t fbn = fb->fec_block_number & 0xffffffu;
         uint64_t nrec = 0;
@@ -197,6 +198,7 @@ protoop_arg_t fec_recover_finish_pre(picoquic_cnx_t *cnx, pquic_fec_block_t *fb,
     const int k = fb->total_source_symbols;
     const uint32_t fbn = fb->fec_block_number & 0xffffffu;
     if (status == FECGPU_BLOCK_REF_UB) FEC_STAT_ADD(ref_ub_blocks, 1);
+    if (status == FECGPU_BLOCK_SINGULAR) __atomic_fetch_add(&g_fec_singular_blocks, 1, __ATOMIC_RELAXED);
     /* first the symbols allocated for sources the reference leaves unrecovered go back to the arena, so
      * an allocation retried below for a recovered one (its pre-allocation had failed) finds their room,
      * as the reference's allocations after decoding would (it allocates only what it recovers).  The
@@ -248,6 +250,7 @@ protoop_arg_t fec_recover_finish_pre_xor(picoquic_cnx_t *cnx, pquic_fec_block_t 
                                          uint16_t maxl, uint64_t *nrec_acc) {
     const int k = fb->total_source_symbols;
     if (status == FECGPU_BLOCK_REF_UB) FEC_STAT_ADD(ref_ub_blocks, 1);
+    if (status == FECGPU_BLOCK_SINGULAR) __atomic_fetch_add(&g_fec_singular_blocks, 1, __ATOMIC_RELAXED);
     for (int j = 0; j < k; j++) {  /* a pre-allocation the engine did not fill goes back first */
         const int got = status == FECGPU_BLOCK_RECOVERED && ((rec[j >> 6] >> (j & 63)) & 1);
         if (!got && pre[j]) {

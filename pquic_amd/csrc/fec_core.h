@@ -24,6 +24,7 @@ extern "C" {
 extern pquic_fec_host_api_t g_fec_api;   /* bound by pquic_fec_bind_host */
 extern int g_fec_bound;
 extern pquic_fec_protoop_stats_t g_fec_stats;
+extern uint64_t g_fec_singular_blocks;   /* full-rank mode: blocks the received repairs do not determine */
 
 static inline uint32_t fec_pad4(uint32_t x) { return (x + 3u) & ~3u; }
 

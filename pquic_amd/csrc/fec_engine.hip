@@ -722,9 +722,12 @@ __host__ __device__ constexpr static inline size_t plan_full_lds_bytes(uint32_t 
   return 768 + (size_t)r * pad16(k) + (size_t)em * pad16(em + k) + 4 * (128 * 5) + 128 + 16;
 }
 
-// One block's full-rank plan by one wave of a one-wave workgroup.  `lds` holds the log/exp tables at
-// 0 and room for plan_full_lds_bytes(k, r).  Every lane must call it; control flow is wave-uniform.
-__device__ void plan_full_wave_block(uint64_t b, int k, int r, uint32_t fbn_base, const uint32_t *fbn,
+// One block's full-rank plan by one wave: a one-wave workgroup (WG = true) or wave 0 of a larger one
+// whose other waves are busy elsewhere (WG = false: every barrier is the wave's own, plan_sync).  `lds`
+// holds the log/exp tables at 0 and room for plan_full_lds_bytes(k, r).  Every lane of the wave must
+// call it; control flow is wave-uniform.
+template <bool WG = true>
+__device__ __forceinline__ void plan_full_wave_block(uint64_t b, int k, int r, uint32_t fbn_base, const uint32_t *fbn,
                                      const uint32_t *seeds, const uint64_t *sp, const uint64_t *rp, uint8_t *ws,
                                      uint8_t *lds) {
   const WsLayout L = ws_layout((uint32_t)k, (uint32_t)r);
@@ -745,7 +748,7 @@ __device__ void plan_full_wave_block(uint64_t b, int k, int r, uint32_t fbn_base
   clip128(q0, q1, r);
   const int cur_ss = __popcll(s0) + __popcll(s1);
   const int m = __popcll(q0) + __popcll(q1);
-  __syncthreads();  // the previous block's LDS reads are done
+  plan_sync<WG>();  // the previous block's LDS reads are done
   if (r == 0 || cur_ss == k || cur_ss + m < k) {
     if (lane == 0) { h[0] = FECGPU_BLOCK_NOTHING; h[1] = 0; }
     return;
@@ -757,14 +760,14 @@ __device__ void plan_full_wave_block(uint64_t b, int k, int r, uint32_t fbn_base
     if (bit128(m0, m1, j)) unk[rank128(m0, m1, j)] = j;
   for (int i = lane; i < r; i += 64)
     if (bit128(q0, q1, i)) cand[rank128(q0, q1, i)] = i;
-  __syncthreads();
+  plan_sync<WG>();
   const uint32_t f = block_fbn(b, fbn_base, fbn);
   for (int e = lane; e < m; e += 64) {  // TinyMT32 row of every received repair
     Tmt t;
     tmt_init(t, repair_seed(seeds, b, r, f, (uint32_t)cand[e]));
     for (int j = 0; j < k; j++) R[e * kpad + j] = tmt_coef(t);
   }
-  __syncthreads();
+  plan_sync<WG>();
   const int w = n + k;
   const int nq = (w + 63) >> 6;  // column registers in use
   int cnt = 0;
@@ -776,7 +779,7 @@ __device__ void plan_full_wave_block(uint64_t b, int k, int r, uint32_t fbn_base
       const uint32_t a = row[unk[pc[t]]];
       fac[t] = a ? LOG[a] : (uint8_t)255;
     }
-    __syncthreads();
+    plan_sync<WG>();
     // candidate row as it would stand at position cnt: A[u] = row[unk[u]]; V[j] = row[j] for a present
     // source, and 1 at its own slot unk[cnt] (the repair itself is the input there), minus the basis
     // (loads unconditional, products selected afterwards: the basis rows' lookups are independent and
@@ -805,7 +808,7 @@ __device__ void plan_full_wave_block(uint64_t b, int k, int r, uint32_t fbn_base
     // pivot: the first missing column where the reduced candidate is non-zero (A columns: c < n <= 128)
     const uint64_t z0 = __ballot(lane < n && wv[0] != 0);
     const uint64_t z1 = __ballot(lane + 64 < n && wv[1] != 0);
-    __syncthreads();  // fac[] has been read by every lane
+    plan_sync<WG>();  // fac[] has been read by every lane
     if ((z0 | z1) == 0) continue;  // dependent on the accepted repairs: never read by the data pass
     const int p = z0 ? __ffsll((unsigned long long)z0) - 1 : 64 + __ffsll((unsigned long long)z1) - 1;
     const uint32_t pv = p < 64 ? (uint32_t)__shfl((int)wv[0], p, 64) : (uint32_t)__shfl((int)wv[1], p - 64, 64);
@@ -821,7 +824,7 @@ __device__ void plan_full_wave_block(uint64_t b, int k, int r, uint32_t fbn_base
       const uint32_t a = B[t * wpad + p];
       fac[t] = a ? LOG[a] : (uint8_t)255;
     }
-    __syncthreads();
+    plan_sync<WG>();
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       if (q >= nq) continue;  // wave-uniform
@@ -846,14 +849,14 @@ __device__ void plan_full_wave_block(uint64_t b, int k, int r, uint32_t fbn_base
       }
     }
     cnt++;
-    __syncthreads();
+    plan_sync<WG>();
   }
   if (cnt < n) {  // the received repairs do not determine the block
     if (lane == 0) { h[0] = FECGPU_BLOCK_SINGULAR; h[1] = 0; }
     return;
   }
   for (int t = lane; t < n; t += 64) rowof[pc[t]] = t;
-  __syncthreads();
+  plan_sync<WG>();
   for (int x = lane; x < n * n; x += 64) {  // a full-rank solution has no undetermined unknowns
     const int i = x / n, u = x - i * n;
     h[L.off_dep + i * em + u] = 0;
@@ -904,7 +907,7 @@ __global__ __launch_bounds__(64) void k_rlc_plan_full(uint64_t nblocks, int k, i
     while (todo) {
       const int g = __ffsll((unsigned long long)todo) - 1;
       todo &= todo - 1;
-      if ((uint32_t)g % parts == part) plan_full_wave_block(base + g, k, r, fbn_base, fbn, seeds, sp, rp, ws, lds);
+      if ((uint32_t)g % parts == part) plan_full_wave_block<true>(base + g, k, r, fbn_base, fbn, seeds, sp, rp, ws, lds);
     }
   }
 }
@@ -2277,11 +2280,13 @@ __global__ __launch_bounds__(kLdsThreads) void k_rlc_encode_lds(const uint8_t *_
                          block_fbn(b, fbn_base, fbn));
 }
 
+// full: room for the full-rank re-plan's scratch as well (a reference-mode launch keeps its size)
 struct DecLdsLayout {
   uint32_t rec, nz, t01, t2, rows, bytes;
-  __host__ __device__ DecLdsLayout(int k, int r, int L, int OT) {
+  __host__ __device__ DecLdsLayout(int k, int r, int L, int OT, int full = 0) {
     const WsLayout W = ws_layout((uint32_t)k, (uint32_t)r);
-    rec = pad16((uint32_t)plan_lds_bytes((uint32_t)k, (uint32_t)r));
+    const size_t pl = plan_lds_bytes((uint32_t)k, (uint32_t)r), pf = plan_full_lds_bytes((uint32_t)k, (uint32_t)r);
+    rec = pad16((uint32_t)(full && pf > pl ? pf : pl));
     nz = rec + W.stride;
     t01 = nz + 16;
     t2 = t01 + 16u * OT * k;
@@ -2292,13 +2297,18 @@ struct DecLdsLayout {
 
 // One block's decode (block b of the mask / seed / status arrays; src_b, rep_b, dst_b: its rows) with
 // its rows staged in LDS, by all kLdsThreads threads; e <= EM unknowns (one pass), the zero /
-// undetermined rule at the end (thread 0).
-template <int EM>
+// undetermined rule at the end (thread 0).  full: full-rank mode -- wave 0 turns the reference plan's
+// record into what the fix-up pass (k_rlc_plan_full) leaves: a record the reference elimination gave
+// up on is planned again from every received repair, a recovered one loses its dependency flags.  The
+// re-plan is compiled in only with FULL (k_block_svc, k_rlc_decode_lds<EM, true>): the kernel of a
+// reference-mode launch keeps its registers (EM 16: 125 VGPRs without it, 143 with it).
+template <int EM, bool FULL>
 __device__ __forceinline__ void decode_block_lds(uint8_t *lds, uint64_t b, const uint8_t *src_b, const uint8_t *rep_b,
                                                  uint8_t *dst_b, int k, int r, int L, uint32_t fbn_base,
                                                  const uint32_t *fbn, const uint32_t *seeds, const uint64_t *sp,
-                                                 const uint64_t *rp, uint8_t *status, uint64_t *recovered, int wreg) {
-  const DecLdsLayout Y(k, r, L, EM);
+                                                 const uint64_t *rp, uint8_t *status, uint64_t *recovered, int wreg,
+                                                 int full) {
+  const DecLdsLayout Y(k, r, L, EM, FULL && full);
   const WsLayout WL = ws_layout((uint32_t)k, (uint32_t)r);
   const int Lp = (int)pad16((uint32_t)L), Lw = L >> 2;
   uint8_t *h = lds + Y.rec;
@@ -2310,6 +2320,17 @@ __device__ __forceinline__ void decode_block_lds(uint8_t *lds, uint64_t b, const
     FEC_STAMP_AT(0);
     plan_load_tables(lds);
     plan_wave_any<false>(wreg, b, k, r, fbn_base, fbn, seeds, sp, rp, h - b * (uint64_t)WL.stride, lds);
+    if (FULL && full) {
+      // the record went out through generic stores: all of them have landed before it is read back
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      const int st0 = __builtin_amdgcn_readfirstlane((int)h[0]);
+      if (st0 == FECGPU_BLOCK_REF_UB) {
+        plan_full_wave_block<false>(b, k, r, fbn_base, fbn, seeds, sp, rp, h - b * (uint64_t)WL.stride, lds);
+      } else if (st0 == FECGPU_BLOCK_RECOVERED) {  // a zero symbol hides no other
+        uint32_t *dep = reinterpret_cast<uint32_t *>(h + WL.off_dep);
+        for (uint32_t x = threadIdx.x; x < (pad16(WL.em * WL.em) >> 2); x += 64) dep[x] = 0u;
+      }
+    }
     if (threadIdx.x == 0) *nzword = 0;
   } else {  // waves 1-7: all k source and r repair rows of the block (absent ones are never read)
     stage_rows_lds(lds + Y.rows, src_b, k, L, Lp, 64);
@@ -2351,7 +2372,7 @@ __device__ __forceinline__ void decode_block_lds(uint8_t *lds, uint64_t b, const
   }
 }
 
-template <int EM>
+template <int EM, bool FULL>
 __global__ __launch_bounds__(kLdsThreads) void k_rlc_decode_lds(const uint8_t *__restrict__ src,
                                                                 const uint8_t *__restrict__ rep, uint64_t nblocks, int k,
                                                                 int r, int L, uint32_t fbn_base, const uint32_t *fbn,
@@ -2360,8 +2381,9 @@ __global__ __launch_bounds__(kLdsThreads) void k_rlc_decode_lds(const uint8_t *_
                                                                 uint8_t *dst, int wreg) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   for (uint64_t b = blockIdx.x; b < nblocks; b += gridDim.x)
-    decode_block_lds<EM>(lds, b, src + b * (uint64_t)k * L, rep + b * (uint64_t)r * L, dst + b * (uint64_t)k * L, k, r,
-                         L, fbn_base, fbn, seeds, sp, rp, status, recovered, wreg);
+    decode_block_lds<EM, FULL>(lds, b, src + b * (uint64_t)k * L, rep + b * (uint64_t)r * L,
+                               dst + b * (uint64_t)k * L, k, r, L, fbn_base, fbn, seeds, sp, rp, status, recovered, wreg,
+                               FULL);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2382,7 +2404,7 @@ constexpr int kSvcMaxR = 128;
 constexpr uint64_t kSvcClaimed = 1ull << 63;
 struct alignas(64) BlockSvcReq {
   uint64_t seq;                     // request number, written last by the host (release); | kSvcClaimed
-  uint32_t op, k, r, L, fbn, wreg;  // op 1 = RLC encode, 2 = RLC decode with per-repair seeds
+  uint32_t op, k, r, L, fbn, wreg;  // op 1 = RLC encode, 2 = RLC decode with per-repair seeds, 3 = the same, full rank
   uint64_t src, rep, dst;           // device addresses of the block's rows (page-locked host memory)
   uint64_t sp[2], rp[2];            // presence masks (decode)
   uint32_t seeds[kSvcMaxR];         // the repairs' FPID seeds (decode)
@@ -2461,9 +2483,10 @@ __global__ __launch_bounds__(kLdsThreads) void k_block_svc(BlockSvcMailbox *mb, 
       uint8_t *st = reinterpret_cast<uint8_t *>(&mb->status);
       uint64_t *rec = mb->recovered;
       // masks and seeds from the LDS copy of the request
-      if (em <= 4) decode_block_lds<4>(lds, 0, src, rep, dst, k, r, L, 0, nullptr, R.seeds, R.sp, R.rp, st, rec, R.wreg);
-      else if (em <= 8) decode_block_lds<8>(lds, 0, src, rep, dst, k, r, L, 0, nullptr, R.seeds, R.sp, R.rp, st, rec, R.wreg);
-      else decode_block_lds<16>(lds, 0, src, rep, dst, k, r, L, 0, nullptr, R.seeds, R.sp, R.rp, st, rec, R.wreg);
+      const int full = R.op == 3;
+      if (em <= 4) decode_block_lds<4, true>(lds, 0, src, rep, dst, k, r, L, 0, nullptr, R.seeds, R.sp, R.rp, st, rec, R.wreg, full);
+      else if (em <= 8) decode_block_lds<8, true>(lds, 0, src, rep, dst, k, r, L, 0, nullptr, R.seeds, R.sp, R.rp, st, rec, R.wreg, full);
+      else decode_block_lds<16, true>(lds, 0, src, rep, dst, k, r, L, 0, nullptr, R.seeds, R.sp, R.rp, st, rec, R.wreg, full);
     }
     if (threadIdx.x == 0)
       __hip_atomic_store(&mb->stamp[2], __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -4113,17 +4136,20 @@ int fecgpu_rlc_decode_apply_packed(const void *src, const void *rep, void *dst, 
                            workspace_bytes, (hipStream_t)stream, em ? (int)em : 1);
 }
 
-int fecgpu_rlc_decode_rows(const uint64_t *src_rows, const uint64_t *rep_rows, uint64_t nblocks, uint32_t k,
-                           uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed, const uint64_t *src_present,
-                           const uint64_t *rep_present, uint8_t *status, uint64_t *recovered, void *workspace,
-                           size_t workspace_bytes, void *stream) {
+// full != 0: full-rank mode.  Its plan names only the repairs it selected and a singular block has
+// no recovered record, so the data pass never reads an unselected repair's address nor any row of a
+// singular block.  (library-internal: host_path.hip's slice loop calls it with the flag)
+extern "C" __attribute__((visibility("hidden"))) int fecgpu_rlc_decode_rows_internal(
+    const uint64_t *src_rows, const uint64_t *rep_rows, uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
+    const uint32_t *rep_seed, const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+    uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream, int full) {
   int rc = decode_args(src_rows, rep_rows, nblocks, k, r, symbol_size, src_present, rep_present, status, recovered,
                        workspace, workspace_bytes);
   if (rc || nblocks == 0) return rc;
   if (r && !rep_seed) return set_err(FECGPU_ERR_INVALID, "%s", "NULL rep_seed");
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = decode_plan_impl(nblocks, k, r, 0, nullptr, rep_seed, src_present, rep_present, workspace,
-                             workspace_bytes, s)))
+  if ((rc = (full ? decode_plan_full_impl : decode_plan_impl)(nblocks, k, r, 0, nullptr, rep_seed, src_present,
+                                                              rep_present, workspace, workspace_bytes, s)))
     return rc;
   count_decode(nblocks);
   uint8_t *ws = (uint8_t *)workspace;
@@ -4142,6 +4168,22 @@ int fecgpu_rlc_decode_rows(const uint64_t *src_rows, const uint64_t *rep_rows, u
   }
   HIPCHK(hipGetLastError());
   return fused ? FECGPU_OK : launch_finalize(nblocks, k, r, status, recovered, ws, s);
+}
+
+int fecgpu_rlc_decode_rows(const uint64_t *src_rows, const uint64_t *rep_rows, uint64_t nblocks, uint32_t k,
+                           uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed, const uint64_t *src_present,
+                           const uint64_t *rep_present, uint8_t *status, uint64_t *recovered, void *workspace,
+                           size_t workspace_bytes, void *stream) {
+  return fecgpu_rlc_decode_rows_internal(src_rows, rep_rows, nblocks, k, r, symbol_size, rep_seed, src_present,
+                                         rep_present, status, recovered, workspace, workspace_bytes, stream, 0);
+}
+
+int fecgpu_rlc_decode_rows_full(const uint64_t *src_rows, const uint64_t *rep_rows, uint64_t nblocks, uint32_t k,
+                                uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream) {
+  return fecgpu_rlc_decode_rows_internal(src_rows, rep_rows, nblocks, k, r, symbol_size, rep_seed, src_present,
+                                         rep_present, status, recovered, workspace, workspace_bytes, stream, 1);
 }
 
 // ---- ragged rows ----
@@ -4353,19 +4395,19 @@ int fecgpu_rlc_encode_rows_fused(const uint64_t *src_rows, const uint32_t *src_l
   return FECGPU_OK;
 }
 
-int fecgpu_rlc_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
-                                 const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
-                                 uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
-                                 const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
-                                 uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream) {
+extern "C" __attribute__((visibility("hidden"))) int fecgpu_rlc_decode_rows_fused_internal(
+    const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows, const uint32_t *rep_len,
+    const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+    const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status, uint64_t *recovered, void *workspace,
+    size_t workspace_bytes, void *stream, int full) {
   int rc = decode_args(src_rows, rep_rows, nblocks, k, r, symbol_size, src_present, rep_present, status, recovered,
                        workspace, workspace_bytes);
   if (rc || nblocks == 0) return rc;
   if (!src_len || !blk_len || (r && !rep_len)) return set_err(FECGPU_ERR_INVALID, "%s", "NULL length table");
   if (r && !rep_seed) return set_err(FECGPU_ERR_INVALID, "%s", "NULL rep_seed");
   hipStream_t s = (hipStream_t)stream;
-  if ((rc = decode_plan_impl(nblocks, k, r, 0, nullptr, rep_seed, src_present, rep_present, workspace,
-                             workspace_bytes, s)))
+  if ((rc = (full ? decode_plan_full_impl : decode_plan_impl)(nblocks, k, r, 0, nullptr, rep_seed, src_present,
+                                                              rep_present, workspace, workspace_bytes, s)))
     return rc;
   count_decode(nblocks);
   uint8_t *ws = (uint8_t *)workspace;
@@ -4381,6 +4423,26 @@ int fecgpu_rlc_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_l
   }
   HIPCHK(hipGetLastError());
   return fused ? FECGPU_OK : launch_finalize(nblocks, k, r, status, recovered, ws, s);
+}
+
+int fecgpu_rlc_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                 const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                 uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                 const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                 uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream) {
+  return fecgpu_rlc_decode_rows_fused_internal(src_rows, src_len, rep_rows, rep_len, blk_len, nblocks, k, r,
+                                               symbol_size, rep_seed, src_present, rep_present, status, recovered,
+                                               workspace, workspace_bytes, stream, 0);
+}
+
+int fecgpu_rlc_decode_rows_fused_full(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                      const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                      uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                      const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                      uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream) {
+  return fecgpu_rlc_decode_rows_fused_internal(src_rows, src_len, rep_rows, rep_len, blk_len, nblocks, k, r,
+                                               symbol_size, rep_seed, src_present, rep_present, status, recovered,
+                                               workspace, workspace_bytes, stream, 1);
 }
 
 // host_path.hip's argument errors (library-internal): the message fecgpu_last_error() returns
@@ -4419,34 +4481,35 @@ static int decode_impl(const void *src, const void *rep, void *dst, uint64_t nbl
   if (rc || nblocks == 0) return rc;
   if (!dst) return set_err(FECGPU_ERR_INVALID, "%s", "NULL output buffer");
   if ((uintptr_t)dst % 4) return set_err(FECGPU_ERR_INVALID, "%s", "output buffer must be 4-byte aligned");
-  if (full) {  // full-rank mode: the one-launch paths below plan in reference mode inside the kernel
-    rc = decode_plan_full_impl(nblocks, k, r, fbn_base, fbn, seeds, sp, rp, ws, wsb, s);
-    if (rc) return rc;
-    return decode_apply_impl(src, rep, dst, nblocks, k, r, L, status, recovered, ws, wsb, s);
-  }
   const WsLayout WL = ws_layout(k, r);
+  // (full-rank mode takes the LDS one-launch path too: its kernel re-plans a given-up block in place)
   // a few blocks with their rows in LDS: one launch, the plan beside the row fetch
   if (nblocks <= kSmallLdsMaxBlocks && r > 0 && WL.em <= 16 && knob(K_PLAN) == 0 && knob(K_SMALL_LDS)) {
-    const DecLdsLayout Y((int)k, (int)r, (int)L, WL.em <= 4 ? 4 : WL.em <= 8 ? 8 : 16);
+    const DecLdsLayout Y((int)k, (int)r, (int)L, WL.em <= 4 ? 4 : WL.em <= 8 ? 8 : 16, full);
     if (Y.bytes <= 65536) {
       count_decode(nblocks);
       const int wreg = knob(K_PLAN) != PLAN_WAVE;
-#define FEC_DEC_LDS(EM)                                                                                          \
-  hipLaunchKernelGGL(k_rlc_decode_lds<EM>, dim3((uint32_t)nblocks), dim3(kLdsThreads), Y.bytes, s, (const uint8_t *)src, \
-                     (const uint8_t *)rep, nblocks, (int)k, (int)r, (int)L, fbn_base, fbn, seeds, sp, rp, status,      \
-                     recovered, (uint8_t *)dst, wreg)
-      if (WL.em <= 4) FEC_DEC_LDS(4);
-      else if (WL.em <= 8) FEC_DEC_LDS(8);
-      else FEC_DEC_LDS(16);
+#define FEC_DEC_LDS(EM, FULL)                                                                                    \
+  hipLaunchKernelGGL((k_rlc_decode_lds<EM, FULL>), dim3((uint32_t)nblocks), dim3(kLdsThreads), Y.bytes, s,         \
+                     (const uint8_t *)src, (const uint8_t *)rep, nblocks, (int)k, (int)r, (int)L, fbn_base, fbn, seeds, \
+                     sp, rp, status, recovered, (uint8_t *)dst, wreg)
+      if (full) {
+        if (WL.em <= 4) FEC_DEC_LDS(4, true);
+        else if (WL.em <= 8) FEC_DEC_LDS(8, true);
+        else FEC_DEC_LDS(16, true);
+      } else if (WL.em <= 4) FEC_DEC_LDS(4, false);
+      else if (WL.em <= 8) FEC_DEC_LDS(8, false);
+      else FEC_DEC_LDS(16, false);
 #undef FEC_DEC_LDS
       HIPCHK(hipGetLastError());
       return FECGPU_OK;
     }
   }
   // the one-launch path: a few blocks, one data pass (e <= 16), the default kernels (no knob forces a
-  // plan kernel or another data path)
+  // plan kernel or another data path).  Reference mode only: the full-rank re-plan inside k_rlc_decode_small
+  // costs it a wave of occupancy (RT 1, VEC 4: 161 -> 196 VGPRs), so full mode goes plan + fix-up + apply
   if (nblocks <= kDecodeSmallMaxBlocks && r > 0 && WL.em <= 16 && knob(K_PLAN) == 0 &&
-      plan_lds_bytes(k, r) <= 65536) {
+      plan_lds_bytes(k, r) <= 65536 && !full) {
     const BsCfg cfg = pick_bs_cfg((int)L);
     const int rt = decode_tile(WL.em);
     if (!use_ring(rt, k, cfg, false)) {
@@ -4458,7 +4521,8 @@ static int decode_impl(const void *src, const void *rep, void *dst, uint64_t nbl
       return FECGPU_OK;
     }
   }
-  rc = decode_plan_impl(nblocks, k, r, fbn_base, fbn, seeds, sp, rp, ws, wsb, s);
+  rc = full ? decode_plan_full_impl(nblocks, k, r, fbn_base, fbn, seeds, sp, rp, ws, wsb, s)
+            : decode_plan_impl(nblocks, k, r, fbn_base, fbn, seeds, sp, rp, ws, wsb, s);
   if (rc) return rc;
   return decode_apply_impl(src, rep, dst, nblocks, k, r, L, status, recovered, ws, wsb, s);
 }
@@ -4801,17 +4865,17 @@ int fecgpu_block_svc_rlc_encode(fecgpu_block_svc_t *v, const void *src, void *re
   return rc;
 }
 
-int fecgpu_block_svc_rlc_decode_seeded(fecgpu_block_svc_t *v, const void *src, const void *rep, void *dst, uint32_t k,
-                                       uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
-                                       const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
-                                       uint64_t *recovered) {
+// op: the request code (2 reference mode, 3 full rank: the mode is the request's own, not the service's)
+static int svc_decode(fecgpu_block_svc_t *v, const void *src, const void *rep, void *dst, uint32_t k, uint32_t r,
+                      uint32_t symbol_size, const uint32_t *rep_seed, const uint64_t *src_present,
+                      const uint64_t *rep_present, uint8_t *status, uint64_t *recovered, uint32_t op) {
   if (!v || !knob(K_BLOCK_SVC)) return FECGPU_ERR_INVALID;
   if (int rc = check_common(src, rep, 1, k, r, symbol_size)) return rc;
   if (!dst || !rep_seed || !src_present || !rep_present || !status || !recovered || r == 0)
     return set_err(FECGPU_ERR_INVALID, "%s", "block service: NULL argument or r == 0");
   const uint32_t em = k < r ? k : r;
   if (em > 16 || r > (uint32_t)kSvcMaxR || knob(K_PLAN) != 0 ||
-      DecLdsLayout((int)k, (int)r, (int)symbol_size, em <= 4 ? 4 : em <= 8 ? 8 : 16).bytes > kSvcLds)
+      DecLdsLayout((int)k, (int)r, (int)symbol_size, em <= 4 ? 4 : em <= 8 ? 8 : 16, op == 3).bytes > kSvcLds)
     return set_err(FECGPU_ERR_INVALID, "%s", "block service: block too large for its LDS");
   uint64_t a[3];
   if (!svc_addr(src, (size_t)k * symbol_size, &a[0]) || !svc_addr(rep, (size_t)r * symbol_size, &a[1]) ||
@@ -4822,7 +4886,7 @@ int fecgpu_block_svc_rlc_decode_seeded(fecgpu_block_svc_t *v, const void *src, c
   HIPCHK(hipGetDevice(&cur));
   if (cur != v->device) HIPCHK(hipSetDevice(v->device));
   BlockSvcReq *m = &v->mb->req;
-  m->op = 2; m->k = k; m->r = r; m->L = symbol_size; m->fbn = 0; m->wreg = knob(K_PLAN) != PLAN_WAVE;
+  m->op = op; m->k = k; m->r = r; m->L = symbol_size; m->fbn = 0; m->wreg = knob(K_PLAN) != PLAN_WAVE;
   m->src = a[0]; m->rep = a[1]; m->dst = a[2];
   m->sp[0] = src_present[0]; m->sp[1] = src_present[1];
   m->rp[0] = rep_present[0]; m->rp[1] = rep_present[1];
@@ -4836,6 +4900,20 @@ int fecgpu_block_svc_rlc_decode_seeded(fecgpu_block_svc_t *v, const void *src, c
     count_decode(1);
   }
   return rc;
+}
+
+int fecgpu_block_svc_rlc_decode_seeded(fecgpu_block_svc_t *v, const void *src, const void *rep, void *dst, uint32_t k,
+                                       uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                       const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                       uint64_t *recovered) {
+  return svc_decode(v, src, rep, dst, k, r, symbol_size, rep_seed, src_present, rep_present, status, recovered, 2);
+}
+
+int fecgpu_block_svc_rlc_decode_full(fecgpu_block_svc_t *v, const void *src, const void *rep, void *dst, uint32_t k,
+                                     uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                     const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                     uint64_t *recovered) {
+  return svc_decode(v, src, rep, dst, k, r, symbol_size, rep_seed, src_present, rep_present, status, recovered, 3);
 }
 
 uint64_t fecgpu_block_svc_launches(const fecgpu_block_svc_t *v) {

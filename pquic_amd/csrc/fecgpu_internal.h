@@ -27,6 +27,17 @@ FECGPU_INTERNAL int fecgpu_rlc_decode_to_internal(const void *src, const void *r
                                                   const uint32_t *fbn, const uint32_t *seeds, const uint64_t *sp,
                                                   const uint64_t *rp, uint8_t *status, uint64_t *recovered, void *ws,
                                                   size_t wsb, void *stream, int full);
+// fec_engine.hip: fecgpu_rlc_decode_rows / _rows_fused; full != 0: full-rank mode (the *_full forms)
+FECGPU_INTERNAL int fecgpu_rlc_decode_rows_internal(const uint64_t *src_rows, const uint64_t *rep_rows, uint64_t nblocks,
+                                                    uint32_t k, uint32_t r, uint32_t symbol_size,
+                                                    const uint32_t *rep_seed, const uint64_t *src_present,
+                                                    const uint64_t *rep_present, uint8_t *status, uint64_t *recovered,
+                                                    void *workspace, size_t workspace_bytes, void *stream, int full);
+FECGPU_INTERNAL int fecgpu_rlc_decode_rows_fused_internal(
+    const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows, const uint32_t *rep_len,
+    const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+    const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status, uint64_t *recovered, void *workspace,
+    size_t workspace_bytes, void *stream, int full);
 // fec_engine.hip: fecgpu_rlc_encode_rows_len with the packed arrays given one by one
 FECGPU_INTERNAL int fecgpu_rlc_encode_rows_len_internal(const uint64_t *src_rows, const uint32_t *src_len,
                                                         const uint64_t *rep_rows, const uint32_t *blk_len,

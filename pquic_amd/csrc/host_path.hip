@@ -599,9 +599,10 @@ int fecgpu_rlc_decode_host_full(fecgpu_host_ctx_t *c, void *src, const void *rep
                      rep_seed, sp, rp, status, recovered, 1);
 }
 
-int fecgpu_rlc_decode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint64_t *rep_rows,
-                                uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
-                                const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+// full != 0: full-rank mode (fecgpu_rlc_decode_rows_full)
+static int decode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint64_t *rep_rows,
+                            uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
+                            const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered, int full) {
   if (!c || !src_rows || (r && (!rep_rows || !seeds)) || !sp || !rp || !status || !recovered) return FECGPU_ERR_INVALID;
   if (!nblocks) return FECGPU_OK;
   std::lock_guard<std::mutex> g(c->mu);
@@ -614,12 +615,24 @@ int fecgpu_rlc_decode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, 
   if (!rc)  // unsliced: the whole batch in one launch
     rc = for_slices(c, nblocks, (size_t)(k + r) * L, nblocks, in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
       HCHK(grow(&w.d_ws, &w.cap_ws, fecgpu_rlc_decode_workspace(m, k, r)));  // one workspace per stream
-      return fecgpu_rlc_decode_rows(t[SRC].at<const uint64_t>(b0), t[REP].at<const uint64_t>(b0), m, k, r, L,
-                                    t[SEED].at<const uint32_t>(b0), t[SP].at<const uint64_t>(b0),
-                                    t[RP].at<const uint64_t>(b0), t[ST].at<uint8_t>(b0), t[REC].at<uint64_t>(b0),
-                                    w.d_ws, w.cap_ws, w.st);
+      return fecgpu_rlc_decode_rows_internal(t[SRC].at<const uint64_t>(b0), t[REP].at<const uint64_t>(b0), m, k, r, L,
+                                             t[SEED].at<const uint32_t>(b0), t[SP].at<const uint64_t>(b0),
+                                             t[RP].at<const uint64_t>(b0), t[ST].at<uint8_t>(b0),
+                                             t[REC].at<uint64_t>(b0), w.d_ws, w.cap_ws, w.st, full);
     });
   return finish(c, unstage_tables(c, t, nblocks, in_place, rc));
+}
+
+int fecgpu_rlc_decode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint64_t *rep_rows,
+                                uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
+                                const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+  return decode_rows_host(c, src_rows, rep_rows, nblocks, k, r, L, seeds, sp, rp, status, recovered, 0);
+}
+
+int fecgpu_rlc_decode_rows_host_full(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint64_t *rep_rows,
+                                     uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
+                                     const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+  return decode_rows_host(c, src_rows, rep_rows, nblocks, k, r, L, seeds, sp, rp, status, recovered, 1);
 }
 
 // ---- ragged rows (fecgpu_rlc_encode_rows_len_host / fecgpu_rlc_decode_rows_len_host) ----
@@ -742,10 +755,11 @@ int fecgpu_rlc_encode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_
   return finish(c, rc);
 }
 
-int fecgpu_rlc_decode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
-                                      const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
-                                      uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
-                                      const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+static int decode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                  const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                  uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
+                                  const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered,
+                                  int full) {
   if (!src_rows || !src_len || !blk_len || (r && (!rep_rows || !rep_len || !seeds)))
     return rows_len_invalid("NULL row / length table");
   if (!sp || !rp || !status || !recovered) return rows_len_invalid("NULL mask/status");
@@ -765,14 +779,31 @@ int fecgpu_rlc_decode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_
     rc = for_slices(c, nblocks, bb, sub_batch(c, nblocks, bb), in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
       HCHK(grow(&w.d_ws, &w.cap_ws, fecgpu_rlc_decode_workspace(m, k, r)));
       // with r == 0 the repair tables have no entries; the device form wants non-NULL ones
-      return fecgpu_rlc_decode_rows_fused(
+      return fecgpu_rlc_decode_rows_fused_internal(
           t[SRC].at<const uint64_t>(b0), t[SLEN].at<const uint32_t>(b0),
           r ? t[REP].at<const uint64_t>(b0) : t[SRC].at<const uint64_t>(b0),
           r ? t[RLEN].at<const uint32_t>(b0) : t[SLEN].at<const uint32_t>(b0), t[BLEN].at<const uint32_t>(b0), m, k, r,
           L, t[SEED].at<const uint32_t>(b0), t[SP].at<const uint64_t>(b0), t[RP].at<const uint64_t>(b0),
-          t[ST].at<uint8_t>(b0), t[REC].at<uint64_t>(b0), w.d_ws, w.cap_ws, w.st);
+          t[ST].at<uint8_t>(b0), t[REC].at<uint64_t>(b0), w.d_ws, w.cap_ws, w.st, full);
     });
   return finish(c, unstage_tables(c, t, nblocks, in_place, rc));
+}
+
+int fecgpu_rlc_decode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                      const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                      uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
+                                      const uint64_t *sp, const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+  return decode_rows_fused_host(c, src_rows, src_len, rep_rows, rep_len, blk_len, nblocks, k, r, L, seeds, sp, rp,
+                                status, recovered, 0);
+}
+
+int fecgpu_rlc_decode_rows_fused_host_full(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                           const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                           uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
+                                           const uint64_t *sp, const uint64_t *rp, uint8_t *status,
+                                           uint64_t *recovered) {
+  return decode_rows_fused_host(c, src_rows, src_len, rep_rows, rep_len, blk_len, nblocks, k, r, L, seeds, sp, rp,
+                                status, recovered, 1);
 }
 
 // ---- XOR on rows (fecgpu_xor_encode_rows_host / fecgpu_xor_decode_rows_host) ----

@@ -35,7 +35,13 @@ struct pquic_fec_scheme {
 pquic_fec_host_api_t g_fec_api;
 int g_fec_bound;
 pquic_fec_protoop_stats_t g_fec_stats;
+uint64_t g_fec_singular_blocks;
 static int g_device;
+/* Full-rank recovery is optional: an engine without its entry points (the CPU stand-in of the sanitizer
+ * builds) leaves these NULL and mode 1 is refused. */
+#pragma weak fecgpu_block_svc_rlc_decode_full
+#pragma weak fecgpu_rlc_decode_host_full
+static int g_recover_mode; /* 0 reference, 1 full rank (pquic_fec_set_recover_mode), under g_mu */
 static fecgpu_host_ctx_t *g_ctx;
 /* the resident single-block service (fecgpu_block_svc_*): one block per call without a kernel launch;
  * calls it refuses (block too large for it, knob off) take the host path */
@@ -77,6 +83,24 @@ int pquic_fec_bind_host(const pquic_fec_host_api_t *api, int device) {
     pthread_mutex_unlock(&g_mu);
     return g_fec_bound ? 0 : -1;
 }
+
+int pquic_fec_set_recover_mode(int mode) {
+    if (mode != 0 && mode != 1) return -1;
+    if (mode == 1 && (fecgpu_block_svc_rlc_decode_full == NULL || fecgpu_rlc_decode_host_full == NULL)) return -1;
+    pthread_mutex_lock(&g_mu);
+    g_recover_mode = mode;
+    pthread_mutex_unlock(&g_mu);
+    return 0;
+}
+
+int pquic_fec_get_recover_mode(void) {
+    pthread_mutex_lock(&g_mu);
+    const int mode = g_recover_mode;
+    pthread_mutex_unlock(&g_mu);
+    return mode;
+}
+
+uint64_t pquic_fec_singular_blocks(void) { return __atomic_load_n(&g_fec_singular_blocks, __ATOMIC_RELAXED); }
 
 void pquic_fec_protoop_stats(pquic_fec_protoop_stats_t *out) {
     out->generate_calls = __atomic_load_n(&g_fec_stats.generate_calls, __ATOMIC_RELAXED);
@@ -236,10 +260,19 @@ static protoop_arg_t recover(picoquic_cnx_t *cnx, int xor_scheme) {
         a->rec[0] = a->rec[1] = 0;
         fec_recover_stage(fb, xor_scheme, maxl, g_src, g_rep, L, a->sp, a->rp, a->seeds);
         fecgpu_block_svc_t *v = xor_scheme ? NULL : svc();
-        rc = v ? fecgpu_block_svc_rlc_decode_seeded(v, g_src, g_rep, g_src, (uint32_t)k, (uint32_t)r, L, a->seeds,
-                                                    a->sp, a->rp, &a->st, a->rec)
-               : FECGPU_ERR_INVALID;
-        if (rc == FECGPU_ERR_INVALID)
+        const int full = !xor_scheme && g_recover_mode == 1;  /* the mode of this call: read under g_mu */
+        if (!v)
+            rc = FECGPU_ERR_INVALID;
+        else if (full)
+            rc = fecgpu_block_svc_rlc_decode_full(v, g_src, g_rep, g_src, (uint32_t)k, (uint32_t)r, L, a->seeds, a->sp,
+                                                  a->rp, &a->st, a->rec);
+        else
+            rc = fecgpu_block_svc_rlc_decode_seeded(v, g_src, g_rep, g_src, (uint32_t)k, (uint32_t)r, L, a->seeds,
+                                                    a->sp, a->rp, &a->st, a->rec);
+        if (rc == FECGPU_ERR_INVALID && full)
+            rc = fecgpu_rlc_decode_host_full(c, g_src, g_rep, 1, (uint32_t)k, (uint32_t)r, L, 0, NULL, a->seeds, a->sp,
+                                             a->rp, &a->st, a->rec);
+        else if (rc == FECGPU_ERR_INVALID)
             rc = xor_scheme ? fecgpu_xor_decode_host(c, g_src, g_rep, 1, (uint32_t)k, L, a->sp, a->rp, &a->st, a->rec)
                             : fecgpu_rlc_decode_host_seeded(c, g_src, g_rep, 1, (uint32_t)k, (uint32_t)r, L, a->seeds,
                                                             a->sp, a->rp, &a->st, a->rec);

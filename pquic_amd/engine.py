@@ -114,6 +114,12 @@ def load_library(path: str = LIB_PATH, private: bool = False):
         L.fecgpu_rlc_decode_rows_fused.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v, v, sz, v]
         L.fecgpu_rlc_encode_rows_fused_host.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v]
         L.fecgpu_rlc_decode_rows_fused_host.argtypes = [v, v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v]
+    if hasattr(L, "fecgpu_rlc_decode_rows_full"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
+        L.fecgpu_rlc_decode_rows_full.argtypes = L.fecgpu_rlc_decode_rows.argtypes
+        L.fecgpu_rlc_decode_rows_host_full.argtypes = L.fecgpu_rlc_decode_rows_host.argtypes
+        L.fecgpu_rlc_decode_rows_fused_full.argtypes = L.fecgpu_rlc_decode_rows_fused.argtypes
+        L.fecgpu_rlc_decode_rows_fused_host_full.argtypes = L.fecgpu_rlc_decode_rows_fused_host.argtypes
+        L.fecgpu_block_svc_rlc_decode_full.argtypes = L.fecgpu_block_svc_rlc_decode_seeded.argtypes
     if hasattr(L, "fecgpu_xor_encode_rows"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
         L.fecgpu_xor_encode_rows.argtypes = [v, v, v, v, u64, u32, u32, v]
         L.fecgpu_xor_decode_rows.argtypes = [v, v, v, v, u64, u32, u32, v, v, v, v, v]
@@ -421,6 +427,30 @@ class Engine:
             _addr(workspace), workspace.numel(), self._stream(stream)), "fecgpu_rlc_decode_rows_fused")
         return status, recovered
 
+    def rlc_decode_rows_full(self, src_rows, rep_rows, rep_seed, src_present, rep_present, status, recovered,
+                             nblocks: int, k: int, r: int, L: int, workspace=None, stream=None):
+        """fecgpu_rlc_decode_rows_full: rows by address in full-rank mode (status RECOVERED or SINGULAR, never
+        REF_UB); a repair full mode does not select is never dereferenced."""
+        if workspace is None:
+            workspace = self.alloc_workspace(nblocks, k, r)
+        self._check(self.lib.fecgpu_rlc_decode_rows_full(
+            _addr(src_rows), _addr(rep_rows), nblocks, k, r, L, _addr(rep_seed), _addr(src_present),
+            _addr(rep_present), _addr(status), _addr(recovered), _addr(workspace), workspace.numel(),
+            self._stream(stream)), "fecgpu_rlc_decode_rows_full")
+        return status, recovered
+
+    def rlc_decode_rows_fused_full(self, src_rows, src_len, rep_rows, rep_len, blk_len, rep_seed, src_present,
+                                   rep_present, status, recovered, nblocks: int, k: int, r: int, L: int,
+                                   workspace=None, stream=None):
+        """fecgpu_rlc_decode_rows_fused_full: rlc_decode_rows_fused in full-rank mode."""
+        if workspace is None:
+            workspace = self.alloc_workspace(nblocks, k, r)
+        self._check(self.lib.fecgpu_rlc_decode_rows_fused_full(
+            _addr(src_rows), _addr(src_len), _addr(rep_rows), _addr(rep_len), _addr(blk_len), nblocks, k, r, L,
+            _addr(rep_seed), _addr(src_present), _addr(rep_present), _addr(status), _addr(recovered),
+            _addr(workspace), workspace.numel(), self._stream(stream)), "fecgpu_rlc_decode_rows_fused_full")
+        return status, recovered
+
     def xor_encode_rows(self, src_rows, src_len, rep_rows, blk_len, nblocks: int, k: int, L: int, stream=None):
         """fecgpu_xor_encode_rows: one pass over rows given by address (u64 tables) and length (u32);
         rep_rows[b] receives exactly blk_len[b] bytes."""
@@ -518,6 +548,21 @@ class HostPath:
                                                              nblocks, k, r, L, _addr(seeds), _addr(sp), _addr(rp),
                                                              _addr(status), _addr(rec)),
                   "fecgpu_rlc_decode_rows_fused_host")
+
+    def rlc_decode_rows_full(self, src_rows, rep_rows, seeds, sp, rp, status, rec, nblocks, k, r, L):
+        """fecgpu_rlc_decode_rows_host_full: host tables, seeds, masks, status and recovered; full-rank mode."""
+        self._chk(self.lib.fecgpu_rlc_decode_rows_host_full(self.ctx, _addr(src_rows), _addr(rep_rows), nblocks, k,
+                                                            r, L, _addr(seeds), _addr(sp), _addr(rp), _addr(status),
+                                                            _addr(rec)), "fecgpu_rlc_decode_rows_host_full")
+
+    def rlc_decode_rows_fused_full(self, src_rows, src_len, rep_rows, rep_len, blk_len, seeds, sp, rp, status, rec,
+                                   nblocks, k, r, L):
+        """fecgpu_rlc_decode_rows_fused_host_full: rlc_decode_rows_fused in full-rank mode."""
+        self._chk(self.lib.fecgpu_rlc_decode_rows_fused_host_full(self.ctx, _addr(src_rows), _addr(src_len),
+                                                                  _addr(rep_rows), _addr(rep_len), _addr(blk_len),
+                                                                  nblocks, k, r, L, _addr(seeds), _addr(sp),
+                                                                  _addr(rp), _addr(status), _addr(rec)),
+                  "fecgpu_rlc_decode_rows_fused_host_full")
 
     def xor_encode_rows(self, src_rows, src_len, rep_rows, blk_len, nblocks, k, L):
         """fecgpu_xor_encode_rows_host: host tables and lengths; the rows must be device-accessible."""
