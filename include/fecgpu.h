@@ -87,6 +87,37 @@ int fecgpu_rlc_window_encode(const void *symbols, uint64_t nwindows, uint32_t st
 int fecgpu_rlc_window_encode_table(const void *symbols, uint64_t nrows, const uint32_t *wrow, uint64_t nwindows,
                                    uint32_t k, uint32_t r, uint32_t symbol_size, void *rep, void *stream);
 
+/* Window encode on rows where they lie (the batching adapter's window jobs in registered arenas):
+ * rows[x] / row_len[x] are the address and length of stream row x -- each symbol once, in order, as in
+ * fecgpu_rlc_window_encode_table -- window w protects rows wrow[w] .. wrow[w] + k - 1 with block number 0,
+ * rep_rows[w * r + i] is the address of its repair i and blk_len[w] its length (the reference's
+ * max_length).  Repair row (w, i) receives exactly blk_len[w] bytes: the first blk_len[w] bytes
+ * fecgpu_rlc_window_encode_table gives on the same rows zero-padded to the width.  Within window w a row
+ * counts as zero from min(row_len, blk_len[w]) on: a row longer than one of its windows is truncated for
+ * that window only.
+ * Two launches: a gather pass lays the stream out once in `workspace` (each row read once, for its own
+ * length -- a symbol serves up to k / step windows and crosses the bus once), then the shared-coefficient
+ * kernel codes the windows from it and stores every repair straight to its row; there is no packed repair
+ * buffer and no scatter pass.
+ * Memory rules (those of the *_rows_fused and XOR row forms): row addresses are 4-byte aligned, below
+ * 2^48, in device memory or mapped page-locked host memory; a row of 0 bytes is never dereferenced and
+ * its address may be 0; a load may touch the aligned dword that holds a row's last byte and nothing after
+ * it; stores are 16-B stores, then dword stores, then byte stores for the last 1-3 bytes; no dword is
+ * read-modify-written; nothing is written past blk_len[w] bytes of a repair row.  All five tables are
+ * device-accessible arrays, so this entry point cannot check them: the kernels clamp blk_len to
+ * symbol_size and row_len to the width instead, and trust wrow[w] + k <= nrows (the host form,
+ * fecgpu_rlc_window_encode_rows_host, checks all three before any launch).  Asynchronous on `stream`,
+ * allocates nothing.
+ * symbol_size is a multiple of 4; internally the width is symbol_size rounded up to 16.  workspace: 16-byte
+ * aligned device memory of fecgpu_rlc_window_rows_workspace(nrows, symbol_size) bytes (nrows rows of the
+ * width).  FECGPU_ERR_INVALID, with a message naming the rule, when (nrows + k) * width reaches 2 GiB (the
+ * kernel's 32-bit load offsets) or knob window_sc is 0. */
+size_t fecgpu_rlc_window_rows_workspace(uint64_t nrows, uint32_t symbol_size);
+int fecgpu_rlc_window_encode_rows(const uint64_t *rows, const uint32_t *row_len, uint64_t nrows,
+                                  const uint32_t *wrow, const uint64_t *rep_rows, const uint32_t *blk_len,
+                                  uint64_t nwindows, uint32_t k, uint32_t r, uint32_t symbol_size,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
 /* RLC encode with every row given by its address: src_rows[b * k + j] / rep_rows[b * r + i] are the
  * device addresses (4-byte aligned; device memory or mapped page-locked host memory, e.g. a registered
  * plugin arena) of source row j / repair row i of block b, each symbol_size bytes.  The tables and
@@ -435,6 +466,19 @@ int fecgpu_rlc_decode_rows_fused_host_full(fecgpu_host_ctx_t *ctx, const uint64_
  * place, others by a copy.  With knob window_sc 0 the windows run through the row-table kernel. */
 int fecgpu_rlc_window_encode_host(fecgpu_host_ctx_t *ctx, const void *symbols, uint64_t nrows, const uint32_t *wrow,
                                   uint64_t nwindows, uint32_t k, uint32_t r, uint32_t symbol_size, void *rep);
+/* fecgpu_rlc_window_encode_rows from the host: the five tables are host arrays (all used in place when
+ * all are page-locked, otherwise all copied once into one device buffer); the rows must be
+ * device-accessible.  The context grows its own stream workspace; the call runs unsliced, one stream
+ * serving all its windows.  Before the context is looked at it checks the shapes, NULL tables,
+ * wrow[w] + k <= nrows, row_len[x] <= symbol_size and blk_len[w] <= symbol_size, and returns
+ * FECGPU_ERR_INVALID with a message naming the rule, nothing written.  With knob window_sc 0, or a stream
+ * past the kernel's 32-bit offsets, the windows are expanded to blocks (src_rows[w * k + j] =
+ * rows[wrow[w] + j]) and run through fecgpu_rlc_encode_rows_fused_host with every block number 0: the same
+ * bytes, each symbol read once per window. */
+int fecgpu_rlc_window_encode_rows_host(fecgpu_host_ctx_t *ctx, const uint64_t *rows, const uint32_t *row_len,
+                                       uint64_t nrows, const uint32_t *wrow, const uint64_t *rep_rows,
+                                       const uint32_t *blk_len, uint64_t nwindows, uint32_t k, uint32_t r,
+                                       uint32_t symbol_size);
 int fecgpu_xor_encode_host(fecgpu_host_ctx_t *ctx, const void *src, void *rep, uint64_t nblocks,
                            uint32_t k, uint32_t symbol_size);
 int fecgpu_xor_decode_host(fecgpu_host_ctx_t *ctx, void *src, const void *rep, uint64_t nblocks,

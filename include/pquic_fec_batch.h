@@ -55,7 +55,7 @@ typedef struct {
     uint64_t flushed_full, flushed_deadline, flushed_drain;
     uint64_t immediate;             /* blocks completed at submit (preconditions failed) */
     uint64_t engine_errors;
-    uint64_t windows, window_rows;  /* window blocks coded from shared streams; stream rows staged for them */
+    uint64_t windows, window_rows;  /* window blocks coded from shared streams; stream rows laid out for them */
     uint64_t engine_us, stage_us;   /* thread time in engine calls / in stager work items (all threads) */
     uint64_t complete_us;           /* caller-thread time in completions (poll / drain) */
     uint64_t rows_in_place;         /* symbol rows the kernels read or wrote where they lie (registered arenas) */
@@ -100,7 +100,12 @@ void pquic_fec_batcher_destroy(pquic_fec_batcher_t *b);
  * the received sources and the repair and writes the recovered source into the symbol allocated at
  * submission for the last missing index, with the XOR operation's FPID (fec_block_number << 8 | j), return
  * value and counters (current_source_symbols stays as it was).  (Against an engine library without those
- * two entry points XOR blocks are staged, packed and zero-padded.)
+ * two entry points XOR blocks are staged, packed and zero-padded.)  Window batches
+ * (pquic_fec_batch_generate_window) use the range too, through fecgpu_rlc_window_encode_rows_host: every
+ * stream symbol in it is handed over once, by address and data_length, the device builds the de-duplicated
+ * stream from those rows, and every repair symbol in it is written where it lies for the window's length;
+ * only symbols outside every registered range go through staging rows.  (Against an engine library without
+ * that entry point the stream is copied into page-locked rows and the repairs are copied out.)
  * Returns 0, or -1 (NULL / empty range, overlap with a registered range, registration failure). */
 int pquic_fec_batch_register_heap(pquic_fec_batcher_t *b, void *base, size_t bytes);
 /* Unregister the range registered at `base` (a connection closing).  No block whose symbols lie in it
@@ -118,8 +123,9 @@ int pquic_fec_batch_generate(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_
 /* Queue fec_generate_repair_symbols (RLC-GF(256)) for a window block of the sliding-window sender
  * (window_framework_sender.h:209-260: malloc_fec_block(cnx, 0) at :215, the symbols in flight chosen by
  * window_select_symbols_to_protect, the generate call at :235).  Same contract and result as
- * pquic_fec_batch_generate; in addition the batch stages each connection's symbols once for all the
- * windows that share them and codes the windows together (every window is block number 0, so they share
+ * pquic_fec_batch_generate; in addition the batch lays each connection's symbols out once, as one stream of
+ * rows, for all the windows that share them (copied into page-locked rows, or with a registered heap handed
+ * over where they lie) and codes the windows together (every window is block number 0, so they share
  * their coefficients).  Windows from one connection should arrive in sending order, as the sender
  * produces them; a block with a non-zero block number is queued as an ordinary block. */
 int pquic_fec_batch_generate_window(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t *fb,

@@ -45,19 +45,21 @@ def sources():
 
 GEN = os.path.join(CSRC, "gen_bitslice.py")
 LENS_HDR = os.path.join(CSRC, "bitslice_lens_gen.h")
+SCROWS_HDR = os.path.join(CSRC, "bitslice_scrows_gen.h")  # written by the same run of the generator
 
 
 def generate_lens_header(force: bool = False) -> str:
     """The length-aware decode bodies are generated, not committed (15 bodies, 1.5 MB of text): write
-    csrc/bitslice_lens_gen.h when it is missing or older than the generator.  bitslice_gen.h is left alone."""
-    if force or not os.path.exists(LENS_HDR) or os.path.getmtime(LENS_HDR) < os.path.getmtime(GEN):
+    csrc/bitslice_lens_gen.h when it is missing or older than the generator, and with it the window bodies that
+    store repairs by address (csrc/bitslice_scrows_gen.h).  bitslice_gen.h is left alone."""
+    if force or any(not os.path.exists(h) or os.path.getmtime(h) < os.path.getmtime(GEN) for h in (LENS_HDR, SCROWS_HDR)):
         env = {k: v for k, v in os.environ.items() if not k.startswith("FEC_GEN")}  # the defaults, always
         _run([sys.executable, GEN, "--lens-only"], env=env)
     return LENS_HDR
 
 
 def up_to_date() -> bool:
-    if not os.path.exists(LIB) or not os.path.exists(LENS_HDR):
+    if not os.path.exists(LIB) or not os.path.exists(LENS_HDR) or not os.path.exists(SCROWS_HDR):
         return False
     hip, c, hdr = sources()
     t = os.path.getmtime(LIB)

@@ -35,7 +35,12 @@
  * connection's symbols once, as one run of rows (a stager lays the runs out at flush: windows grouped
  * by connection, each window matched against the run's tail by symbol identity), records where each
  * window starts, and the engine codes all windows from that stream with the shared-coefficient kernel
- * (fecgpu_rlc_window_encode_host) after one copy of the stream to the device.
+ * (fecgpu_rlc_window_encode_host) after one copy of the stream to the device.  With a heap registered a
+ * window job gathers too (fecgpu_rlc_window_encode_rows_host, a weak reference like the others): the run
+ * layout is the same, but a stream row that lies in an arena is handed over by address and length instead
+ * of copied, the device builds the stream from the rows, and a repair whose symbol lies in an arena is
+ * written there by the kernel for the window's length; only symbols outside every arena go through the
+ * staging rows, unpadded.
  * Finished jobs are completed on the caller's thread in poll / drain with the same finish
  * halves the synchronous operations use (fec_core.c), so a batched block ends in exactly the
  * state the protocol operation would leave it in.  The caller keeps a block unmodified until
@@ -82,6 +87,9 @@ static int full_rank_available(void) {
 static int xor_rows_available(void) {
     return fecgpu_xor_encode_rows_host != NULL && fecgpu_xor_decode_rows_host != NULL;
 }
+/* And window jobs on rows where they lie: without it a window job's stream is copied into the staging rows. */
+#pragma weak fecgpu_rlc_window_encode_rows_host
+static int window_rows_available(void) { return fecgpu_rlc_window_encode_rows_host != NULL; }
 
 enum { OP_GENERATE = 0, OP_RECOVER = 1, OP_WINDOW = 2 /* generate, window blocks */ };
 #define GENERATES(op) ((op) != OP_RECOVER)
@@ -120,9 +128,11 @@ typedef struct job {
     int rc;
     int post;                      /* 1 once the engine ran: work items copy repairs out */
     uint32_t next_chunk, chunks_done;  /* staging work items claimed / finished (under the batcher lock) */
-    int gather;                    /* row tables: RLC through the _rows / _rows_len forms, XOR through fecgpu_xor_*_rows_host */
+    int gather;                    /* row tables: RLC through the _rows / _rows_len forms, XOR through fecgpu_xor_*_rows_host,
+                                    * windows through fecgpu_rlc_window_encode_rows_host */
     uint64_t *srow, *rrow;         /* pinned: [cap][k] source / [cap][r] repair row device addresses (recover:
-                                    * a missing source's entry is the row its recovered bytes go to) */
+                                    * a missing source's entry is the row its recovered bytes go to; window:
+                                    * srow[q] / slen[q] are stream row q, at most cap * k of them) */
     pquic_source_symbol_t **pre;   /* recover gather: [cap][k] symbols allocated at submission for the missing
                                     * sources (written in place by the kernel), NULL where none */
     uint64_t *cpm;                 /* recover gather: [cap][2] missing sources whose recovered row is staged
@@ -342,7 +352,7 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
     }
     /* gather tables (generate or recover with a registered heap; XOR where the engine has its row forms):
      * grown on reuse like the repair table */
-    j->gather = (op == OP_GENERATE || op == OP_RECOVER) && (!xor_scheme || xor_rows_available()) &&
+    j->gather = (op == OP_WINDOW ? window_rows_available() : !xor_scheme || xor_rows_available()) &&
                 __atomic_load_n(&b->nheaps, __ATOMIC_RELAXED) > 0;
     if (j->gather && op == OP_RECOVER && j->pre_cap < (size_t)cap * k) {
         free(j->pre);
@@ -384,6 +394,8 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
     }
     /* the XOR row forms take a length per row and nothing else: no tables, no gather */
     if (j->gather && xor_scheme && !(j->slen && j->rlen && j->blen)) j->gather = 0;
+    /* so does the window form: a length per stream row and per window */
+    if (j->gather && op == OP_WINDOW && !(j->slen && j->blen)) j->gather = 0;
     j->ragged = 0;
     j->ncopy = 0;
     if (op == OP_WINDOW) {  /* window tables: start rows (page-locked), the stream's symbols, the grouping */
@@ -521,7 +533,10 @@ static job_t *job_get(pquic_fec_batcher_t *b, int op, int xor_scheme, uint32_t k
 
 static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
     const uint32_t S = j->stride;
-    if (j->op == OP_WINDOW)
+    if (j->op == OP_WINDOW && j->gather)
+        j->rc = fecgpu_rlc_window_encode_rows_host(c, j->srow, j->slen, j->nrows, j->wrow, j->rrow, j->blen, j->n, j->k,
+                                                   j->r, S);
+    else if (j->op == OP_WINDOW)
         j->rc = fecgpu_rlc_window_encode_host(c, j->src, j->nrows, j->wrow, j->n, j->k, j->r, S, j->rep);
     else if (j->gather && j->xor_scheme && j->op == OP_RECOVER)
         j->rc = fecgpu_xor_decode_rows_host(c, j->srow, j->slen, j->rrow, j->blen, j->n, j->k, S, j->sp, j->rp, j->st,
@@ -820,8 +835,14 @@ static void stage_blocks(job_t *j, uint32_t i0, uint32_t i1) {
 /* Window job: the stream layout, then its rows.  Entries are grouped by connection (stable), and a
  * connection's windows extend one run of rows: a window whose first symbol is among the run's last
  * rows, and whose symbols continue the run as far as it goes, starts there and appends only its new
- * symbols; any other window starts a fresh run of its k symbols.  Rows are zero-padded to the stride
- * (the reference pads each window's symbols to its max_length, which the copy-out then keeps). */
+ * symbols; any other window starts a fresh run of its k symbols.  Without row tables the rows are copied,
+ * zero-padded to the stride (the reference pads each window's symbols to its max_length, which the copy-out
+ * then keeps).  A gather job (a heap registered, an engine with the window row form) copies no row that
+ * lies in a registered heap: the table takes its device address and data_length; only a symbol outside
+ * every heap is copied, unpadded, into its staging row, and the table points there.  Repairs likewise: one
+ * whose symbol lies in a heap for the window's length is written there by the kernel, any other into its
+ * staging row and copied out as before.  Each stream row and each repair row counts once in rows_in_place /
+ * rows_staged. */
 static int cmp_cnx(const void *a, const void *b, void *arg) {
     const job_t *j = arg;
     const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b;
@@ -829,8 +850,8 @@ static int cmp_cnx(const void *a, const void *b, void *arg) {
     return cx != cy ? (cx < cy ? -1 : 1) : (x > y) - (x < y);
 }
 
-static void stage_windows(job_t *j) {
-    const uint32_t S = j->stride, k = j->k;
+static void stage_windows(pquic_fec_batcher_t *b, job_t *j) {
+    const uint32_t S = j->stride, k = j->k, r = j->r;
     for (uint32_t i = 0; i < j->n; i++) j->order[i] = i;
     qsort_r(j->order, j->n, sizeof *j->order, cmp_cnx, j);
     uint64_t nrows = 0, run = 0;  /* run: first row of the current connection's run */
@@ -855,6 +876,50 @@ static void stage_windows(job_t *j) {
         for (uint64_t x = nrows - start; x < k; x++) j->rowsym[nrows++] = ss[x];
     }
     j->nrows = nrows;
+    if (j->gather) {
+        uint64_t inplace = 0, staged = 0;
+        uint32_t ncopy = 0;
+        int hint = -1;
+        pthread_rwlock_rdlock(&b->heaps_mu);
+        for (uint64_t q = 0; q < nrows; q++) {
+            const pquic_source_symbol_t *sym = j->rowsym[q];
+            const uint16_t n = sym ? sym->data_length : 0;
+            uint64_t d = n ? heap_dev(b, sym->data, n, &hint) : 0;
+            if (d) {
+                inplace++;
+            } else {
+                if (n) memcpy(j->src + q * S, sym->data, n);
+                d = j->src_dev + q * S;  /* a row of no bytes is never read */
+                staged += n != 0;
+            }
+            j->srow[q] = d;
+            j->slen[q] = n;
+        }
+        for (uint32_t i = 0; i < j->n; i++) {
+            const entry_t *e = &j->ent[i];
+            uint8_t cp = 0;
+            j->blen[i] = e->maxl;
+            for (uint32_t x = 0; x < r; x++) {
+                pquic_repair_symbol_t *rs = (int)x < e->nalloc ? j->reps[(size_t)i * r + x] : NULL;
+                uint64_t d = rs && e->maxl ? heap_dev(b, rs->data, e->maxl, &hint) : 0;
+                if (!d) {
+                    d = j->rep_dev + ((size_t)i * r + x) * S;
+                    cp |= rs != NULL;
+                    staged += rs != NULL;
+                } else {
+                    inplace++;
+                }
+                j->rrow[(size_t)i * r + x] = d;
+            }
+            j->copy[i] = cp;
+            ncopy += cp;
+        }
+        pthread_rwlock_unlock(&b->heaps_mu);
+        j->ncopy = ncopy;
+        __atomic_fetch_add(&b->stats.rows_in_place, inplace, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&b->stats.rows_staged, staged, __ATOMIC_RELAXED);
+        return;
+    }
     for (uint64_t q = 0; q < nrows; q++) {
         const pquic_source_symbol_t *sym = j->rowsym[q];
         const uint16_t n = sym ? sym->data_length : 0;
@@ -931,7 +996,7 @@ static void *stager_main(void *arg) {
         const uint64_t t0 = mono_us();
         const uint32_t i0 = c * STAGE_CHUNK, i1 = i0 + STAGE_CHUNK < j->n ? i0 + STAGE_CHUNK : j->n;
         if (j->post) copy_out_blocks(j, i0, i1);
-        else if (j->op == OP_WINDOW) stage_windows(j);
+        else if (j->op == OP_WINDOW) stage_windows(b, j);
         else if (j->gather) gather_blocks(b, j, i0, i1);
         else stage_blocks(j, i0, i1);
         const uint64_t dt = mono_us() - t0;

@@ -24,6 +24,8 @@
 //   k_rows_gather / k_rows_scatter   ragged rows (a length per row) to and from a packed batch, around
 //                  the packed encode / decode: the *_rows_len entry points.
 //   k_xor_encode_rows / k_xor_decode_rows   XOR on rows given by address, a length per row, in one pass.
+//   k_rlc_encode_sc / _sc_rows   window encode on shared coefficients, 2 KiB chunks of the windows x bytes
+//                  space; _sc_rows stores every repair to its row address for the window's own length.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -50,6 +52,8 @@
 #else
 #include "bitslice_lens_gen.h"
 #endif
+// the window bodies that store repairs to rows by address: written by the same run of the generator
+#include "bitslice_scrows_gen.h"
 #include "../../include/fecgpu.h"
 #include "fecgpu_internal.h"
 
@@ -2706,6 +2710,94 @@ static bool launch_encode_sc(const uint8_t *sym, uint8_t *rep, uint64_t nwin, in
   return true;
 }
 
+// The same chunks with the repairs stored where they belong (fecgpu_rlc_window_encode_rows): the stream
+// is the gathered one (row x at sym + x * L, zeros past its length), window w begins at row wrow[w], and
+// repair i of window w goes to the address rep_rows[w * r + i], blk_len[w] bytes of it (clamped to
+// `cap`, the caller's symbol_size).  A source byte at or past the window's length only reaches repair
+// bytes that are not stored, so a row longer than one of its windows is truncated for that window
+// alone.  Per piece the lane carries the table entry of its window, its offset in the row and its byte
+// count below the length; the bodies' epilogue (gen_bitslice.py, scrows_put) does the rest.
+#define BS_CALL_ENCSCL(RT)                                                                                   \
+  bs_encscl_r##RT##_v16(sp, (uint64_t)L, (uint64_t)L, (uint32_t)k, (uint32_t)k, (uint32_t)rt, lds_addr(lds), \
+                        off[0], off[1], tp[0], tp[1], tq[0], tq[1], nb[0], nb[1], vm[0], vm[1], vs[0], vs[1])
+template <int RT>
+__global__ __launch_bounds__(64) void k_rlc_encode_sc_rows(const uint8_t *__restrict__ sym,
+                                                           const uint32_t *__restrict__ wrow,
+                                                           const uint64_t *__restrict__ rep_rows,
+                                                           const uint32_t *__restrict__ blk_len, uint64_t nwin, int k,
+                                                           int r, int L, int cap, int r0) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  constexpr int CSB = FEC_BS_COEF_ROW_BYTES(RT);
+  const int lane = threadIdx.x;
+  const int rt = r - r0 < RT ? r - r0 : RT;
+  if (lane < RT) {  // coefficient rows of repairs r0 .. r0 + rt - 1, seed (0 << 8) | i: as k_rlc_encode_sc
+    uint16_t *row0 = reinterpret_cast<uint16_t *>(lds);
+    uint16_t *row = row0 + FEC_BS_FIELD_SLOT(RT, lane);
+    if (lane < rt) {
+      Tmt t;
+      tmt_init(t, rlc_seed(0u, (uint32_t)(r0 + lane)));
+      for (int j = 0; j < k; j++) row[j * (CSB / 2)] = FEC_BS_FIELD(tmt_coef(t), lane);
+    } else {
+      for (int j = 0; j < k; j++) row[j * (CSB / 2)] = 0;
+    }
+    if constexpr (RT < 4) {
+      if (lane == 0)
+        for (int j = 0; j < k; j++)
+          for (int x = RT; x < 4; x++) row0[j * (CSB / 2) + FEC_BS_FIELD_SLOT(RT, x)] = 0;
+    }
+  }
+  __syncthreads();
+  const uint64_t F = nwin * (uint64_t)L;
+  const uint64_t nch = (F + 2047) / 2048;
+  const uint64_t sp = (uint64_t)(uintptr_t)sym;
+  for (uint64_t c = blockIdx.x; c < nch; c += gridDim.x) {
+    const uint64_t F0 = c * 2048;
+    uint32_t off[2], tq[2], nb[2];
+    uint64_t tp[2], vm[2], vs[2];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const uint64_t p = F0 + 16u * (uint32_t)(lane + 64 * q);
+      const bool ok = p < F;
+      const uint64_t w = ok ? p / (uint64_t)L : 0;  // a piece past the end reads row 0 and stores nothing
+      const uint32_t t = ok ? (uint32_t)(p - w * (uint64_t)L) : 0u;
+      uint32_t bl = ok ? blk_len[w] : 0u;
+      if (bl > (uint32_t)cap) bl = (uint32_t)cap;
+      off[q] = ok ? wrow[w] * (uint32_t)L + t : 0u;
+      tq[q] = t;
+      nb[q] = bl > t ? (bl - t < 16u ? bl - t : 16u) : 0u;
+      tp[q] = (uint64_t)(uintptr_t)(rep_rows + w * (uint64_t)r + (uint64_t)r0);
+      vm[q] = __ballot(nb[q] == 16u);
+      vs[q] = __ballot(nb[q] != 0u && nb[q] < 16u);
+    }
+    if constexpr (RT == 1) BS_CALL_ENCSCL(1);
+    else if constexpr (RT == 2) BS_CALL_ENCSCL(2);
+    else if constexpr (RT == 4) BS_CALL_ENCSCL(4);
+    else BS_CALL_ENCSCL(8);
+  }
+}
+
+// The limits are launch_encode_sc's for a start table: knob window_sc, and load offsets that fit 32 bits.
+static bool launch_encode_sc_rows(const uint8_t *sym, const uint32_t *wrow, const uint64_t *rep_rows,
+                                  const uint32_t *blk_len, uint64_t nrows, uint64_t nwin, int k, int r, int L, int cap,
+                                  hipStream_t s) {
+  if (!knob(K_WINDOW_SC) || L % 16 || (uintptr_t)sym % 16) return false;
+  if ((nrows + (uint64_t)k) * (uint64_t)L >= (1ull << 31)) return false;
+  const uint64_t nch = (nwin * (uint64_t)L + 2047) / 2048;
+  const size_t lds = (size_t)k * FEC_BS_COEF_ROW_BYTES(8);
+  for (int r0 = 0; r0 < r; r0 += 8) {
+    const int rt = r - r0 < 8 ? r - r0 : 8;
+#define SC_ROWS_GO(RT)                                                                                          \
+  hipLaunchKernelGGL((k_rlc_encode_sc_rows<RT>), dim3(grid_for(nch)), dim3(64), lds, s, sym, wrow, rep_rows, blk_len, \
+                     nwin, k, r, L, cap, r0)
+    if (rt >= 5) SC_ROWS_GO(8);
+    else if (rt >= 3) SC_ROWS_GO(4);
+    else if (rt == 2) SC_ROWS_GO(2);
+    else SC_ROWS_GO(1);
+#undef SC_ROWS_GO
+  }
+  return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // LDS-ring data path (bs2_* bodies, gen_bitslice.py body2): the sources of a group stream into a
 // per-wave LDS ring by LDS-DMA, D-1 rows ahead (up to 1 KiB per wave-instruction, linear in memory
@@ -4228,6 +4320,43 @@ int fecgpu_rows_scatter(const void *src, const uint64_t *rows, const uint32_t *l
                         uint32_t symbol_size, void *stream) {
   if (int rc = rows_args(rows, len, src, nrows, symbol_size)) return rc;
   return launch_scatter(src, rows, len, nrows, symbol_size, nullptr, nullptr, nullptr, 1, 0, (hipStream_t)stream);
+}
+
+// ---- window jobs on rows: gather the stream once, code it with the repairs stored by address ----
+static uint32_t window_rows_width(uint32_t symbol_size) { return (symbol_size + 15u) & ~15u; }
+
+size_t fecgpu_rlc_window_rows_workspace(uint64_t nrows, uint32_t symbol_size) {
+  return (size_t)nrows * window_rows_width(symbol_size);
+}
+
+int fecgpu_rlc_window_encode_rows(const uint64_t *rows, const uint32_t *row_len, uint64_t nrows, const uint32_t *wrow,
+                                  const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nwindows, uint32_t k,
+                                  uint32_t r, uint32_t symbol_size, void *workspace, size_t workspace_bytes,
+                                  void *stream) {
+  if (nwindows == 0) return FECGPU_OK;
+  if (!rows || !row_len || !wrow || !rep_rows || !blk_len)
+    return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: NULL table");
+  int rc = check_common(rows, rep_rows, nwindows, k, r, symbol_size);
+  if (rc) return rc;
+  if (r == 0) return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: r out of range [1,128]");
+  if (nrows < k) return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: stream shorter than k");
+  if (!workspace || (uintptr_t)workspace % 16)
+    return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: workspace missing or not 16-byte aligned");
+  const uint32_t W = window_rows_width(symbol_size);
+  if (!knob(K_WINDOW_SC) || (nrows + (uint64_t)k) * (uint64_t)W >= (1ull << 31))
+    return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: stream of 2 GiB or more, or window_sc knob 0");
+  if (workspace_bytes < fecgpu_rlc_window_rows_workspace(nrows, symbol_size))
+    return set_err(FECGPU_ERR_NOMEM, "%s", "window rows workspace too small");
+  if (int rc2 = bs_table_check()) return rc2;
+  hipStream_t s = (hipStream_t)stream;
+  // the gather clamps a row's length to the width; what lies at or past symbol_size never reaches a stored byte
+  if ((rc = launch_gather(rows, row_len, nrows, W, workspace, nullptr, nullptr, 1, s))) return rc;
+  if (!launch_encode_sc_rows((const uint8_t *)workspace, wrow, rep_rows, blk_len, nrows, nwindows, (int)k, (int)r,
+                             (int)W, (int)symbol_size, s))
+    return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: stream of 2 GiB or more, or window_sc knob 0");
+  HIPCHK(hipGetLastError());
+  count_encode(nwindows);
+  return FECGPU_OK;
 }
 
 // ---- XOR on rows ----

@@ -41,6 +41,9 @@ OUT = os.environ.get("FEC_GEN_OUT") or os.path.join(HERE, "bitslice_gen.h")
 # repository: pquic_amd/build.py writes it before it compiles (`gen_bitslice.py --lens-only`, which leaves
 # OUT alone), and fec_engine.hip includes it after OUT, whose macros and case table it uses.
 OUT_LENS = os.path.join(os.path.dirname(OUT), "bitslice_lens_gen.h")
+# The window bodies that store repairs to rows given by address (bs_encscl_*) go to a third header, written
+# by the same `--lens-only` run and not kept in the repository either.
+OUT_SCROWS = os.path.join(os.path.dirname(OUT), "bitslice_scrows_gen.h")
 
 # ----------------------------------------------------------------------------- register map
 # T64: the exchange rounds shift two words per instruction (v_lshlrev_b64 / v_lshrrev_b64 on an
@@ -673,7 +676,187 @@ def selfcheck_lens():
                 assert ex == live and mem == row[:n] + b"\xA5" * (cb + 8 - n), (VEC, cb, n)
 
 
-def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False, lens: bool = False):
+# ============================================================================ window repairs by address
+# The shared-coefficient bodies with repairs stored to rows given by address (bs_encscl_*, the kernel
+# k_rlc_encode_sc_rows).  A lane's two 16-B pieces may lie in different windows, so everything about a
+# store is per piece and per lane: %[tp{q}] points at the entry of the piece's window and of the tile's
+# first repair in the table of repair row addresses, %[t{q}] is the piece's byte offset in its row,
+# %[nb{q}] the number of its bytes below the window's length (0..16), %[vm{q}] the lanes with nb == 16
+# and %[vs{q}] those with 0 < nb < 16.
+# * The epilogue first requests the addresses of all rt rows for both pieces into the source buffers
+#   (dead by then: one block per call, nsrc == k) and waits for them once, after the first transpose.
+# * A full piece is one 16-B store.  The one piece per window that straddles its length stores its whole
+#   dwords, then the last 1-3 bytes one by one; a piece past the length stores nothing.  No load, no
+#   read-modify-write, nothing past the window's length.
+def scrows_addr_loads(RT, base):
+    out = []
+    for i in range(RT):
+        out += [f"s_cmp_le_u32 s{S_RT}, {i}", "s_cbranch_scc1 .Lrowsld_%="]  # no entry past the tile's rt rows
+        for q in range(2):
+            out.append(f"global_load_dwordx2 v[{base + 4 * i + 2 * q}:{base + 4 * i + 2 * q + 1}], %[tp{q}], off offset:{8 * i}")
+    out.append(".Lrowsld_%=:")
+    return out
+
+
+def scrows_put(accs, A, q, live, tag):
+    """The piece's nb bytes of the row in accs (4 dwords) to the row whose address sits in v[A:A+1]."""
+    T0, T1, T2 = TMP[0], TMP[1], TMP[2]
+    ad = f"v[{A}:{A + 1}]"
+    nb = f"%[nb{q}]"
+    out = [f"v_add_co_u32 v{A}, vcc, v{A}, %[t{q}]",
+           f"v_addc_co_u32 v{A + 1}, vcc, 0, v{A + 1}, vcc",
+           f"s_mov_b64 exec, %[vm{q}]",
+           f"global_store_dwordx4 {ad}, {regrange(accs[0], 4)}, off@STPOL@",
+           f"s_mov_b64 exec, %[vs{q}]",
+           f"s_cbranch_execz .Lnostr_{tag}_%="]
+    for d in range(3):  # whole dwords below the length: the lanes narrow as d grows
+        out += [f"v_cmpx_le_u32 vcc, {4 * d + 4}, {nb}",
+                f"global_store_dword {ad}, v{accs[d]}, off" + (f" offset:{4 * d}" if d else "") + "@STPOL@"]
+    out += [f"s_mov_b64 exec, %[vs{q}]",
+            f"v_lshrrev_b32 v{T1}, 2, {nb}",  # the dword that holds the last byte
+            f"v_cmp_eq_u32 vcc, 1, v{T1}",
+            f"v_cndmask_b32 v{T0}, v{accs[0]}, v{accs[1]}, vcc",
+            f"v_cmp_eq_u32 vcc, 2, v{T1}",
+            f"v_cndmask_b32 v{T0}, v{T0}, v{accs[2]}, vcc",
+            f"v_cmp_eq_u32 vcc, 3, v{T1}",
+            f"v_cndmask_b32 v{T0}, v{T0}, v{accs[3]}, vcc",
+            f"v_and_b32 v{T2}, -4, {nb}",
+            f"v_add_co_u32 v{A}, vcc, v{A}, v{T2}",
+            f"v_addc_co_u32 v{A + 1}, vcc, 0, v{A + 1}, vcc",
+            f"v_and_b32 v{T1}, 3, {nb}",
+            f"v_lshrrev_b32 v{T2}, 8, v{T0}",
+            f"v_cmpx_lt_u32 vcc, 0, v{T1}",
+            f"global_store_byte {ad}, v{T0}, off@STPOL@",
+            f"v_cmpx_lt_u32 vcc, 1, v{T1}",
+            f"global_store_byte {ad}, v{T2}, off offset:1@STPOL@",
+            f"v_cmpx_lt_u32 vcc, 2, v{T1}",
+            f"global_store_byte_d16_hi {ad}, v{T0}, off offset:2@STPOL@",
+            f".Lnostr_{tag}_%=:",
+            f"s_mov_b64 exec, {live}"]
+    return out
+
+
+def simulate_scrows(lines, vg, ops, masks, mem):
+    """Run what scrows_put emits on 64 lanes.  vg[lane]: VGPRs, ops[name][lane]: the per-lane value of
+    operand %[name], masks[name]: the lanes of an exec operand, mem: {address: byte}, written by stores."""
+    import re
+    M = 0xFFFFFFFF
+    ex = list(masks["live"])
+    vcc = [0] * 64
+    labels = {ln[:-1]: i for i, ln in enumerate(lines) if ln.endswith(":")}
+
+    def val(t, l):
+        p = re.match(r"%\[(\w+)\]", t)
+        if p:
+            return ops[p.group(1)][l]
+        return vg[l][int(t[1:])] if t.startswith("v") else int(t, 0) & M
+    pc = 0
+    while pc < len(lines):
+        ln = lines[pc].replace("@STPOL@", "")
+        pc += 1
+        if ln.endswith(":"):
+            continue
+        op, _, rest = ln.partition(" ")
+        a = [x.strip() for x in rest.split(",")]
+        if op == "s_mov_b64":
+            assert a[0] == "exec", ln
+            p = re.match(r"%\[(\w+)\]", a[1])
+            ex = list(masks[p.group(1) if p else "live"])
+        elif op == "s_cbranch_execz":
+            if not any(ex):
+                pc = labels[a[0]]
+        elif op in ("v_cmpx_le_u32", "v_cmpx_lt_u32", "v_cmp_eq_u32"):
+            assert a[0] == "vcc", ln
+            for l in range(64):
+                if ex[l]:
+                    x, y = val(a[1], l), val(a[2], l)
+                    vcc[l] = int(x <= y if "_le_" in op else x < y if "_lt_" in op else x == y)
+                    if op.startswith("v_cmpx"):
+                        ex[l] = bool(vcc[l])
+        elif op in ("v_add_co_u32", "v_addc_co_u32"):
+            assert a[1] == "vcc" and (op == "v_add_co_u32" or a[4] == "vcc"), ln
+            for l in range(64):
+                if ex[l]:
+                    res = val(a[2], l) + val(a[3], l) + (vcc[l] if op == "v_addc_co_u32" else 0)
+                    vg[l][int(a[0][1:])], vcc[l] = res & M, res >> 32
+        elif op == "v_cndmask_b32":
+            assert a[3] == "vcc", ln
+            for l in range(64):
+                if ex[l]:
+                    vg[l][int(a[0][1:])] = val(a[2], l) if vcc[l] else val(a[1], l)
+        elif op in ("v_and_b32", "v_lshrrev_b32"):
+            for l in range(64):
+                if ex[l]:
+                    x, y = val(a[1], l), val(a[2], l)
+                    vg[l][int(a[0][1:])] = x & y if op == "v_and_b32" else y >> x
+        elif op.startswith("global_store_"):
+            A = int(re.match(r"v\[(\d+):", a[0]).group(1))
+            p = re.match(r"v\[(\d+):(\d+)\]|v(\d+)", a[1])
+            r0 = int(p.group(1) or p.group(3))
+            io = re.search(r"offset:(\d+)", a[2])
+            io = int(io.group(1)) if io else 0
+            assert a[2].startswith("off"), ln
+            for l in range(64):
+                if not ex[l]:
+                    continue
+                ad = (vg[l][A] | (vg[l][A + 1] << 32)) + io
+                if op == "global_store_dwordx4" or op == "global_store_dword":
+                    assert ad % 4 == 0, ln
+                    for i in range(4 if op.endswith("x4") else 1):
+                        for t in range(4):
+                            mem[ad + 4 * i + t] = (vg[l][r0 + i] >> (8 * t)) & 0xFF
+                else:
+                    assert op in ("global_store_byte", "global_store_byte_d16_hi"), ln
+                    mem[ad] = (vg[l][r0] >> (16 if op.endswith("hi") else 0)) & 0xFF
+        else:
+            raise AssertionError(ln)
+    return ex
+
+
+def selfcheck_scrows():
+    """scrows_put against a byte model, with the piece setup of k_rlc_encode_sc_rows: chunks of 2 KiB
+    over windows of width 48 (a lane's pieces in different windows) and 2064 (a window over two chunks),
+    window lengths around every store class.  Every repair row receives exactly its window's length of
+    the bytes the lanes hold, each byte written once, and nothing else is written."""
+    rnd = random.Random(5)
+    A0, AD = 100, 120
+    for W, lens in ((48, [0, 1, 3, 4, 15, 16, 17, 31, 32, 33, 47, 48] * 8), (2064, [2063, 2064, 1, 1029])):
+        nwin = len(lens)
+        F = nwin * W
+        rowaddr = [0x7f0000001000 + 0x100000 * w + 4 * (w % 3) + (0xfffffff0 if w == 1 else 0) for w in range(nwin)]
+        want, got = {}, {}
+        data = bytes(rnd.randrange(1, 256) for _ in range(F))
+        for w in range(nwin):
+            for t in range(lens[w]):
+                want[rowaddr[w] + t] = data[w * W + t]
+        for c in range((F + 2047) // 2048):
+            ops = {n: [0] * 64 for n in ("t0", "t1", "nb0", "nb1")}
+            masks = {"live": [True] * 64, "vm0": [False] * 64, "vm1": [False] * 64, "vs0": [False] * 64, "vs1": [False] * 64}
+            vg = [{r: rnd.getrandbits(32) for r in range(60, 130)} for _ in range(64)]
+            for l in range(64):
+                for q in range(2):
+                    p = c * 2048 + 16 * (l + 64 * q)
+                    ok = p < F
+                    w = p // W if ok else 0
+                    t = p - w * W if ok else 0
+                    nb = min(max(lens[w] - t, 0), 16) if ok else 0
+                    ops[f"t{q}"][l], ops[f"nb{q}"][l] = t, nb
+                    masks[f"vm{q}"][l], masks[f"vs{q}"][l] = nb == 16, 0 < nb < 16
+                    vg[l][AD + 2 * q], vg[l][AD + 2 * q + 1] = rowaddr[w] & 0xFFFFFFFF, rowaddr[w] >> 32
+                    for i in range(4):
+                        vg[l][A0 + 4 * q + i] = int.from_bytes(data[p + 4 * i:p + 4 * i + 4].ljust(4, b"\0"), "little") if ok \
+                            else rnd.getrandbits(32)
+            for q in range(2):
+                wrote = {}
+                ex = simulate_scrows(scrows_put([A0 + 4 * q + i for i in range(4)], AD + 2 * q, q, "live", f"q{q}"),
+                                     vg, ops, masks, wrote)
+                assert ex == masks["live"]
+                assert not set(wrote) & set(got), (W, c, q)  # no byte is written twice
+                got.update(wrote)
+        assert got == want, (W, len(got), len(want))
+
+
+def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False, lens: bool = False, rows: bool = False):
     """Inline-asm text for one group of blocks x one column chunk.
 
     The sources of all blocks of the group form ONE stream (flattened index s = g*k + j),
@@ -681,7 +864,9 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False, lens: bool = Fa
     per-block epilogue subroutine (reached by s_swappc) transposes the accumulators back,
     stores them and clears them.  mode 'enc' (addresses by stride) or 'dec' (addresses
     from LDS tables written by the wrapper).  lens ('dec' only): the length-aware variant, every
-    table entry carries its row's byte bound in bits 48-63 (see the section above lens_loads)."""
+    table entry carries its row's byte bound in bits 48-63 (see the section above lens_loads).
+    rows (shared-coefficient 'enc' only): the epilogue stores to row addresses read from a table, each
+    piece for its own byte count (see the section above scrows_addr_loads)."""
     ld, st, nw = LOADOP[VEC]
     NP = 32 // VEC
     DATA_BASE = data_base(mode)
@@ -696,6 +881,7 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False, lens: bool = Fa
     TA = acc_base + 8 * RT  # touch: the row address (pair), the dropped data, the lane offset
     TD, TOFF = TA + 2, TA + 3
     assert acc_base + 8 * RT + (4 if touch else 0) <= 256
+    assert not rows or (mode == "enc" and sc and VEC == 16 and T64 and not EXECMASK and 4 * RT <= 8 * P)
     assert not touch or (touch >= 2 and (NP + 1) * (P - 1) + 1 <= 63)
     L = []
     a = L.append
@@ -729,7 +915,8 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False, lens: bool = Fa
         a(f"s_mov_b32 s{S_C[3]}, 0")
     if mode == "enc":
         a(f"s_mov_b64 s[{S_CUR}:{S_CUR + 1}], %[src]")
-        a(f"s_mov_b64 s[{S_OUT}:{S_OUT + 1}], %[rep]")
+        if not rows:
+            a(f"s_mov_b64 s[{S_OUT}:{S_OUT + 1}], %[rep]")
     else:
         a(f"v_mov_b32 v{INPTR}, %[intab]")
         a(f"ds_read_b64 v[{NADDR}:{NADDR + 1}], v{INPTR}")  # source 0's address
@@ -941,7 +1128,10 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False, lens: bool = Fa
 
     # ---- per-block epilogue subroutine ----
     a(".Lepi_%=:")
-    if mode == "enc":
+    if rows:
+        a(f"s_mov_b32 s{S_RT}, %[rt]")
+        L.extend(scrows_addr_loads(RT, DATA_BASE))
+    elif mode == "enc":
         a(f"s_mov_b64 s[{S_O2}:{S_O2 + 1}], s[{S_OUT}:{S_OUT + 1}]")
         a(f"s_mov_b32 s{S_RT}, %[rt]")
     elif epi_pf:
@@ -1001,6 +1191,12 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False, lens: bool = Fa
                 continue
             a(f"v_readfirstlane_b32 s{S_O2}, v{TMP[2]}")
             a(f"v_readfirstlane_b32 s{S_O2 + 1}, v{TMP[3]}")
+        if rows:
+            if i == 0:  # the row addresses, requested before the first transpose
+                a("s_waitcnt vmcnt(0)")
+            for q in range(NP):
+                L.extend(scrows_put(accs[q * nw:q * nw + nw], DATA_BASE + 4 * i + 2 * q, q, live, f"r{i}q{q}"))
+            continue
         for q in range(NP):
             a(f"s_mov_b64 exec, %[vm{q}]")
             a(f"{st} %[{'so' if sc else 'off'}{q}], {regrange(accs[q * nw], nw)}, s[{S_O2}:{S_O2 + 1}]@STPOL@")
@@ -1012,8 +1208,9 @@ def body(mode: str, RT: int, VEC: int, P: int, sc: bool = False, lens: bool = Fa
     for r in range(acc_base, acc_base + 8 * RT):
         a(f"v_mov_b32 v{r}, 0")
     if mode == "enc":
-        a(f"s_add_u32 s{S_OUT}, s{S_OUT}, %[rslo]")  # next block of the group (64-bit step)
-        a(f"s_addc_u32 s{S_OUT + 1}, s{S_OUT + 1}, %[rshi]")
+        if not rows:  # rows: one block per call (nsrc == k), no next block to step to
+            a(f"s_add_u32 s{S_OUT}, s{S_OUT}, %[rslo]")  # next block of the group (64-bit step)
+            a(f"s_addc_u32 s{S_OUT + 1}, s{S_OUT + 1}, %[rshi]")
     else:
         a(f"v_add_u32 v{OUTPTR}, {DEC_REC_BYTES}, v{OUTPTR}")
     a(f"s_setpc_b64 s[{S_RET}:{S_RET + 1}]")
@@ -1038,18 +1235,27 @@ def cstring(lines):
     return "\n".join(out)
 
 
-def emit_function(mode, RT, VEC, P, sc=False, lens=False):
+def emit_function(mode, RT, VEC, P, sc=False, lens=False, rows=False):
     """sc: the shared-coefficient encode (window blocks, fbn 0): separate per-piece store offsets
     so0.. (a lane's pieces may belong to different windows, whose sources and repairs are laid
-    out with different strides).  lens: the length-aware decode family bs_decl_*."""
-    lines, top = body(mode, RT, VEC, P, sc, lens) if lens else body(mode, RT, VEC, P, sc)
+    out with different strides).  lens: the length-aware decode family bs_decl_*.  rows (with sc): the
+    family bs_encscl_*, repairs stored to rows given by address for each window's own length."""
+    lines, top = body(mode, RT, VEC, P, sc, lens, rows)
     NP = 32 // VEC
-    name = f"bs_{mode}{'sc' if sc else ''}{'l' if lens else ''}_r{RT}_v{VEC}"
+    name = f"bs_{mode}{'sc' if sc else ''}{'l' if lens or rows else ''}_r{RT}_v{VEC}"
     offs = ", ".join(f"uint32_t off{q}" for q in range(NP))
-    if sc:
+    if rows:
+        offs += "".join(f", uint64_t tp{q}" for q in range(NP)) + "".join(f", uint32_t t{q}" for q in range(NP)) + \
+            "".join(f", uint32_t nb{q}" for q in range(NP))
+    elif sc:
         offs += ", " + ", ".join(f"uint32_t so{q}" for q in range(NP))
     vms = ", ".join(f"uint64_t vm{q}" for q in range(NP))
-    if mode == "enc":
+    if rows:
+        vms += "".join(f", uint64_t vs{q}" for q in range(NP))
+        sig = (f"__device__ __forceinline__ void {name}(uint64_t src, uint64_t sdl, uint64_t ll, "
+               f"uint32_t nsrc, uint32_t k, uint32_t rt, uint32_t coef, {offs}, {vms})")
+        ins = ['[src] "s"(src)', '[sdl] "s"(sdl)', '[ll] "s"(ll)', '[rt] "s"(rt)']
+    elif mode == "enc":
         sig = (f"__device__ __forceinline__ void {name}(uint64_t src, uint64_t rep, uint32_t L, uint32_t rslo, "
                f"uint32_t rshi, uint64_t sdl, uint64_t ll, "
                f"uint32_t nsrc, uint32_t k, uint32_t rt, uint32_t coef, {offs}, {vms})")
@@ -1060,9 +1266,14 @@ def emit_function(mode, RT, VEC, P, sc=False, lens=False):
         ins = ['[intab] "v"(intab)', '[outtab] "v"(outtab)']
     ins += ['[nsrc] "s"(nsrc)', '[k] "s"(k)', '[coef] "v"(coef)']
     ins += [f'[off{q}] "v"(off{q})' for q in range(NP)]
-    if sc:
+    if rows:
+        for n in ("tp", "t", "nb"):
+            ins += [f'[{n}{q}] "v"({n}{q})' for q in range(NP)]
+    elif sc:
         ins += [f'[so{q}] "v"(so{q})' for q in range(NP)]
     ins += [f'[vm{q}] "s"(vm{q})' for q in range(NP)]
+    if rows:
+        ins += [f'[vs{q}] "s"(vs{q})' for q in range(NP)]
     sclob = SGPR_CLOBBER + (SGPR_CLOBBER_LENS if lens else [])
     clob = [f'"v{r}"' for r in range(T_BASE, top)] + [f'"s{r}"' for r in sclob] + ['"vcc"', '"scc"', '"memory"']
     out = [sig + " {", "  asm volatile(", cstring(lines), "      :",
@@ -1742,6 +1953,33 @@ def main_lens():
         f.write("\n".join(parts))
     os.replace(tmp, OUT_LENS)
     print(f"wrote {OUT_LENS}: {len(CONFIGS)} bodies, max VGPR {max(tops.values())}")
+    main_scrows()
+
+
+def main_scrows():
+    """bitslice_scrows_gen.h: the shared-coefficient encode bodies that store each window's repairs to rows
+    given by address (fecgpu_rlc_window_encode_rows).  bs_encsc_* in bitslice_gen.h stay as they are."""
+    selfcheck_scrows()
+    parts = ["// GENERATED by pquic_amd/csrc/gen_bitslice.py -- do not edit.",
+             "// Window bodies bs_encscl_* (see the generator, 'window repairs by address'); included after",
+             "// bitslice_gen.h, whose macros and case table they use.",
+             "#pragma once",
+             "#include <hip/hip_runtime.h>",
+             "#include <stdint.h>",
+             ""]
+    tops = {}
+    for RT in (1, 2, 4, 8):
+        P = prefetch_depth("enc", RT, 16)
+        fn, top = emit_function("enc", RT, 16, P, sc=True, rows=True)
+        fn = fn.replace('" FEC_LD_POL "', '" FEC_LD_POL_SC "')  # as bs_encsc_*: overlapping windows re-read rows from L2
+        tops[("encscl", RT, 16, P)] = top
+        parts.append(fn)
+        parts.append("")
+    tmp = OUT_SCROWS + ".tmp"  # whole or not at all: a build may be interrupted
+    with open(tmp, "w") as f:
+        f.write("\n".join(parts))
+    os.replace(tmp, OUT_SCROWS)
+    print(f"wrote {OUT_SCROWS}: 4 bodies, max VGPR {max(tops.values())}")
 
 
 if __name__ == "__main__":

@@ -755,6 +755,54 @@ int fecgpu_rlc_encode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_
   return finish(c, rc);
 }
 
+// ---- window jobs on rows (fecgpu_rlc_window_encode_rows_host) ----
+// Unsliced: one gathered stream in slot 0's d_src serves all the windows.  The five tables have two
+// entry counts (stream rows, windows), so each goes to stage_tables as one block of its whole size.
+int fecgpu_rlc_window_encode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *rows, const uint32_t *row_len,
+                                       uint64_t nrows, const uint32_t *wrow, const uint64_t *rep_rows,
+                                       const uint32_t *blk_len, uint64_t nwin, uint32_t k, uint32_t r, uint32_t L) {
+  if (!rows || !row_len || !wrow || !rep_rows || !blk_len) return rows_len_invalid("NULL row / length / window table");
+  if (int rc = rows_len_shape(k, r, L)) return rc;
+  if (r == 0) return rows_len_invalid("r out of range [1,128]");
+  for (uint64_t w = 0; w < nwin; w++) {
+    if ((uint64_t)wrow[w] + k > nrows) return rows_len_invalid("window past the stream: wrow + k above nrows");
+    if (blk_len[w] > L) return rows_len_invalid("blk_len above symbol_size");
+  }
+  for (uint64_t x = 0; x < nrows; x++)
+    if (row_len[x] > L) return rows_len_invalid("row_len above symbol_size");
+  if (!c) return rows_len_invalid("NULL host context");
+  if (!nwin) return FECGPU_OK;
+  const size_t W = (L + 15u) & ~(size_t)15;
+  if (!fecgpu_knob_window_sc() || (nrows + (uint64_t)k) * W >= (1ull << 31)) {
+    // the windows as blocks of their own, every block number 0; a row counts for min(row_len, blk_len[w])
+    std::vector<uint64_t> src(nwin * (size_t)k);
+    std::vector<uint32_t> len(nwin * (size_t)k), zero_fbn(nwin, 0u);
+    for (uint64_t w = 0; w < nwin; w++)
+      for (uint32_t j = 0; j < k; j++) {
+        src[w * k + j] = rows[wrow[w] + j];
+        len[w * k + j] = std::min(row_len[wrow[w] + j], blk_len[w]);
+      }
+    return fecgpu_rlc_encode_rows_fused_host(c, src.data(), len.data(), rep_rows, blk_len, nwin, k, r, L, zero_fbn.data());
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  HCHK(hipSetDevice(c->device));
+  enum { ROWS, RLEN, WROW, REP, BLEN };
+  Table t[] = {in(rows, nrows * 8), in(row_len, nrows * 4), in(wrow, nwin * 4), in(rep_rows, nwin * r * 8),
+               in(blk_len, nwin * 4)};
+  bool in_place;
+  int rc = stage_tables(c, t, 1, &in_place);
+  Slot &s = c->slot[0];  // the stream that carries the copies of staged tables
+  do {
+    if (rc) break;
+    const size_t need = fecgpu_rlc_window_rows_workspace(nrows, L);
+    LCHK(grow(&s.d_src, &s.cap_src, need));
+    rc = fecgpu_rlc_window_encode_rows(t[ROWS].at<const uint64_t>(0), t[RLEN].at<const uint32_t>(0), nrows,
+                                       t[WROW].at<const uint32_t>(0), t[REP].at<const uint64_t>(0),
+                                       t[BLEN].at<const uint32_t>(0), nwin, k, r, L, s.d_src, s.cap_src, s.st);
+  } while (0);
+  return finish(c, rc);
+}
+
 static int decode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
                                   const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
                                   uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,

@@ -125,6 +125,13 @@ def load_library(path: str = LIB_PATH, private: bool = False):
         L.fecgpu_xor_decode_rows.argtypes = [v, v, v, v, u64, u32, u32, v, v, v, v, v]
         L.fecgpu_xor_encode_rows_host.argtypes = [v, v, v, v, v, u64, u32, u32]
         L.fecgpu_xor_decode_rows_host.argtypes = [v, v, v, v, v, u64, u32, u32, v, v, v, v]
+    if hasattr(L, "fecgpu_rlc_window_encode_rows"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
+        L.fecgpu_rlc_window_rows_workspace.argtypes = [u64, u32]
+        L.fecgpu_rlc_window_rows_workspace.restype = sz
+        L.fecgpu_rlc_window_encode_rows.argtypes = [v, v, u64, v, v, v, u64, u32, u32, u32, v, sz, v]
+        L.fecgpu_rlc_window_encode_rows_host.argtypes = [v, v, v, u64, v, v, v, u64, u32, u32, u32]
+    if hasattr(L, "fecgpu_rlc_window_encode_table"):
+        L.fecgpu_rlc_window_encode_table.argtypes = [v, u64, v, u64, u32, u32, u32, v, v]
     if not private:
         _lib = L
     return L
@@ -208,6 +215,29 @@ class Engine:
         self._check(self.lib.fecgpu_rlc_window_encode(_addr(symbols), nwindows, step, k, r, L, _addr(rep),
                                                       self._stream(stream)), "fecgpu_rlc_window_encode")
         return rep
+
+    def rlc_window_encode_table(self, symbols, nrows: int, wrow, rep, nwindows: int, k: int, r: int, L: int,
+                                stream=None):
+        """fecgpu_rlc_window_encode_table: window w = rows wrow[w] .. wrow[w] + k - 1 of a packed stream of
+        nrows rows (wrow: u32 device array), block number 0; L % 16 == 0."""
+        self._check(self.lib.fecgpu_rlc_window_encode_table(_addr(symbols), nrows, _addr(wrow), nwindows, k, r, L,
+                                                            _addr(rep), self._stream(stream)),
+                    "fecgpu_rlc_window_encode_table")
+        return rep
+
+    def window_rows_workspace_bytes(self, nrows: int, L: int) -> int:
+        return int(self.lib.fecgpu_rlc_window_rows_workspace(nrows, L))
+
+    def rlc_window_encode_rows(self, rows, row_len, nrows: int, wrow, rep_rows, blk_len, nwindows: int, k: int,
+                               r: int, L: int, workspace=None, stream=None):
+        """fecgpu_rlc_window_encode_rows: stream rows by address and length (u64 / u32 device arrays), window w
+        = rows wrow[w] .. wrow[w] + k - 1; repair row rep_rows[w*r+i] receives exactly blk_len[w] bytes."""
+        if workspace is None:
+            n = self.window_rows_workspace_bytes(nrows, L)
+            workspace = self.torch.empty(max(n, 16), dtype=self.torch.uint8, device=f"cuda:{self.device}")
+        self._check(self.lib.fecgpu_rlc_window_encode_rows(
+            _addr(rows), _addr(row_len), nrows, _addr(wrow), _addr(rep_rows), _addr(blk_len), nwindows, k, r, L,
+            _addr(workspace), workspace.numel(), self._stream(stream)), "fecgpu_rlc_window_encode_rows")
 
     def write_repair_frames(self, rep, frames, nblocks: int, r: int, L: int, data_length: int, frame_stride: int,
                             nss: int, nrs: int, fbn_base: int = 0, fbn=None, stream=None):
@@ -574,3 +604,11 @@ class HostPath:
         self._chk(self.lib.fecgpu_xor_decode_rows_host(self.ctx, _addr(src_rows), _addr(src_len), _addr(rep_rows),
                                                        _addr(blk_len), nblocks, k, L, _addr(sp), _addr(rp),
                                                        _addr(status), _addr(rec)), "fecgpu_xor_decode_rows_host")
+
+    def rlc_window_encode_rows(self, rows, row_len, nrows, wrow, rep_rows, blk_len, nwindows, k, r, L):
+        """fecgpu_rlc_window_encode_rows_host: host tables (stream rows, lengths, window starts, repair rows,
+        window lengths); the rows must be device-accessible."""
+        self._chk(self.lib.fecgpu_rlc_window_encode_rows_host(self.ctx, _addr(rows), _addr(row_len), nrows,
+                                                              _addr(wrow), _addr(rep_rows), _addr(blk_len),
+                                                              nwindows, k, r, L),
+                  "fecgpu_rlc_window_encode_rows_host")

@@ -691,16 +691,25 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
  * windows coded on the shared-coefficient kernel) or pquic_fec_batch_generate (0: every window a block
  * of its own).  Symbols live in per-connection rings sized past the windows that can be in flight.
  * out: [0] stream GiB/s (new symbols protected), [1] p50 us, [2] p99 us, [3] max us, [4] batches,
- *      [5] wall s, [6] windows completed, [7] window GiB/s (k symbols per window).  Returns 0 or -1. */
-int bl_run_window(int device, int k, int r, int L, int step, int nconn, long nwindows, unsigned batch_blocks,
-                  unsigned max_delay_us, int nstreams, int window_api, double out[8]) {
+ *      [5] wall s, [6] windows completed, [7] window GiB/s (k symbols per window).  Returns 0 or -1.
+ * run_window is both entry points: register_heap != 0 registers the arena that holds the symbols and the
+ * repairs with the batcher (window jobs then gather: rows handed over where they lie), and after
+ * bl_set_ragged the batcher is opened for max_symbol bytes and every symbol's length is drawn as in the
+ * ragged block legs (symbol q of a connection is packet q % k of pool block q / k); out[0] and out[7]
+ * then count the bytes the symbols hold. */
+static int run_window(int device, int k, int r, int L, int step, int nconn, long nwindows, unsigned batch_blocks,
+                      unsigned max_delay_us, int nstreams, int window_api, int register_heap, double out[8]) {
     if (k < 1 || k > 64 || r < 1 || step < 1 || nconn < 1 || L < 1 || L > 2048) return -1;
+    const int ragged = register_heap >= 0 && g_ragged_max > 0;  /* bl_run_window itself keeps equal lengths */
+    if (ragged && (g_ragged_max < L || g_ragged_max > 2048)) return -1;
+    if (register_heap < 0) register_heap = 0;
     pquic_fec_host_api_t api = {bl_get, bl_set, bl_malloc, bl_free, NULL};
     if (pquic_fec_bind_host(&api, device)) return -1;
     cpu_set_t saved, near;
     const int pinned = !sched_getaffinity(0, sizeof saved, &saved) && !near_cpus(device, &saved, &near) &&
                        !sched_setaffinity(0, sizeof near, &near);
-    pquic_fec_batch_cfg_t cfg = {device, batch_blocks, max_delay_us, (uint32_t)L, nstreams, g_poll_blocks};
+    pquic_fec_batch_cfg_t cfg = {device, batch_blocks, max_delay_us, (uint32_t)(ragged ? g_ragged_max : L), nstreams,
+                                 g_poll_blocks};
     pquic_fec_batcher_t *b = pquic_fec_batcher_create(&cfg);
     if (!b) return -1;
     const long nslots = (long)batch_blocks * 4 + nconn + 64;
@@ -709,6 +718,7 @@ int bl_run_window(int device, int k, int r, int L, int step, int nconn, long nwi
     if (arena_map(&g_thread_arena, ((size_t)nslots * r * 2 + 1024) * SLOT + pool_bytes, 0)) return -1;
     uint8_t *pool = g_thread_arena.base;
     g_thread_arena.used = (pool_bytes + 63) & ~(size_t)63;
+    if (register_heap && pquic_fec_batch_register_heap(b, g_thread_arena.base, g_thread_arena.bytes)) return -1;
     slot_t *slots = calloc(nslots, sizeof *slots);
     pquic_source_symbol_t *rings = calloc((size_t)nconn * ring, sizeof *rings);
     long *sent = calloc(nconn, sizeof *sent);
@@ -727,12 +737,14 @@ int bl_run_window(int device, int k, int r, int L, int step, int nconn, long nwi
     uint64_t t0 = 0;
     pquic_fec_batch_stats_t st0;
     memset(&st0, 0, sizeof st0);
+    uint64_t new_bytes = 0, win_bytes = 0;  /* the measured pass: bytes of the new symbols, of the windows' symbols */
     for (int pass = 0; pass < 2; pass++) {
         const long nw = pass ? nwindows : nwindows / 5 + 1;
         if (pass) {
             pquic_fec_batch_drain(b);
             pquic_fec_batch_get_stats(b, &st0);
             g_nlat = 0;
+            new_bytes = win_bytes = 0;
         }
         t0 = now_us();
         for (long w = 0; w < nw; w++) {
@@ -745,11 +757,15 @@ int bl_run_window(int device, int k, int r, int L, int step, int nconn, long nwi
                 pquic_source_symbol_t *sym = &rc[q % ring];
                 sym->fpid.raw = (uint32_t)q;
                 sym->data = pool + (size_t)((q * 31 + c * 977) % (long)pool_syms) * L;
-                sym->data_length = (uint16_t)L;
+                sym->data_length = ragged ? ragged_len(c, q / k, (int)(q % k), k, L) : (uint16_t)L;
+                if (ragged && q >= sent[c]) new_bytes += sym->data_length;
             }
             sent[c] += step;
             memset(&s->fb, 0, sizeof s->fb);
-            for (int j = 0; j < k; j++) s->fb.source_symbols[j] = &rc[(sent[c] - k + j) % ring];
+            for (int j = 0; j < k; j++) {
+                s->fb.source_symbols[j] = &rc[(sent[c] - k + j) % ring];
+                if (ragged) win_bytes += s->fb.source_symbols[j]->data_length;
+            }
             s->fb.current_source_symbols = s->fb.total_source_symbols = (uint8_t)k;
             s->fb.total_repair_symbols = (uint8_t)r;
             s->busy = 1;
@@ -768,19 +784,35 @@ int bl_run_window(int device, int k, int r, int L, int step, int nconn, long nwi
     pquic_fec_batch_get_stats(b, &st);
     pquic_fec_batcher_destroy(b);
     qsort(g_lat, g_nlat, sizeof *g_lat, cmp_u64);
-    out[0] = (double)nwindows * step * L / wall / 1073741824.0;
+    out[0] = (ragged ? (double)new_bytes : (double)nwindows * step * L) / wall / 1073741824.0;
     out[1] = g_nlat ? (double)g_lat[g_nlat / 2] : 0;
     out[2] = g_nlat ? (double)g_lat[(long)(g_nlat * 0.99)] : 0;
     out[3] = g_nlat ? (double)g_lat[g_nlat - 1] : 0;
     out[4] = (double)(st.batches - st0.batches);
     out[5] = wall;
     out[6] = (double)(st.completed - st0.completed);
-    out[7] = (double)nwindows * k * L / wall / 1073741824.0;
+    out[7] = (ragged ? (double)win_bytes : (double)nwindows * k * L) / wall / 1073741824.0;
+    g_rows[0] = (double)(st.rows_in_place - st0.rows_in_place);
+    g_rows[1] = (double)(st.rows_staged - st0.rows_staged);
     free(slots); free(rings); free(sent); free(g_lat); free(cnx);
     g_lat = NULL;
     if (pinned) sched_setaffinity(0, sizeof saved, &saved);
     arena_unmap(&g_thread_arena);
     return 0;
+}
+
+int bl_run_window(int device, int k, int r, int L, int step, int nconn, long nwindows, unsigned batch_blocks,
+                  unsigned max_delay_us, int nstreams, int window_api, double out[8]) {
+    return run_window(device, k, r, L, step, nconn, nwindows, batch_blocks, max_delay_us, nstreams, window_api, -1, out);
+}
+
+/* The same window sender (the window API) with the symbols in a registered arena (register_heap 1; 0: the
+ * arena is not registered and the batcher stages every row, the baseline), and with bl_set_ragged's lengths
+ * when they are set.  bl_last_rows then gives the measured pass's rows in place / staged. */
+int bl_run_window_rows(int device, int k, int r, int L, int step, int nconn, long nwindows, unsigned batch_blocks,
+                       unsigned max_delay_us, int nstreams, int register_heap, double out[8]) {
+    return run_window(device, k, r, L, step, nconn, nwindows, batch_blocks, max_delay_us, nstreams, 1,
+                      register_heap != 0, out);
 }
 
 /* Latency of the synchronous drop-in hooks: one block per call, exactly as the block framework
