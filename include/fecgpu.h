@@ -530,6 +530,44 @@ int fecgpu_block_svc_rlc_decode_full(fecgpu_block_svc_t *svc, const void *src, c
                                      uint32_t k, uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
                                      const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
                                      uint64_t *recovered);
+/* Row requests: one block with every row given by its address and its own length, so a caller whose
+ * symbols lie in page-locked memory (a registered plugin arena) stages and copies nothing.  Semantics,
+ * memory rules and clamping are those of fecgpu_rlc_encode_rows_fused, fecgpu_rlc_decode_rows_fused,
+ * fecgpu_rlc_decode_rows_fused_full (full != 0), fecgpu_xor_encode_rows and fecgpu_xor_decode_rows applied
+ * to one block of length blk_len (any value from 1 to 65532; it need not be a multiple of 4): a present
+ * row is read for min(its length, blk_len) bytes; an absent row and a row of 0 bytes are never
+ * dereferenced and may have address 0; a load may touch the aligned dword that holds a row's last byte
+ * and nothing after it; each output row -- every repair (encode), the missing source's own entry of
+ * src_rows (decode) -- receives exactly blk_len bytes by dword stores, then byte stores for the last 1-3
+ * bytes, and no dword is read-modify-written; a block that is not RECOVERED writes no row.  One difference
+ * from the launch forms: the worker fetches a block's rows while it plans the block, so the present rows
+ * of an RLC block may be read before its status is known (a block the masks alone leave at NOTHING still
+ * reads nothing) -- every present row of non-zero length must be readable, also a repair full mode would
+ * not select.
+ * All tables are plain host arrays, copied into the mailbox by the call: src_rows / src_len [k], rep_rows /
+ * rep_len / rep_seed [r], the masks [2].  Row addresses are device addresses (what
+ * fecgpu_host_device_address returns for page-locked host memory, or device memory), 4-byte aligned and
+ * below 2^48.  status and recovered are host words.  Checked before anything is posted, FECGPU_ERR_INVALID
+ * with a message and nothing written: the alignment and the 2^48 bound of every row that is read or
+ * written, k in 1..128, r in 1..128, blk_len in 1..65532, and for the encodes src_len[j] <= blk_len (the
+ * decodes truncate a received symbol longer than the block, as the reference does).  Refused with
+ * FECGPU_ERR_INVALID like the packed calls, computed with L = blk_len rounded up to 4: RLC decode with
+ * min(k, r) > 16 or knob plan non-zero, RLC rows beyond the worker's LDS, knob block_svc 0, a request
+ * withdrawn at its deadline -- the caller then takes a launch form (fecgpu_rlc_encode_rows_fused_host
+ * ...) with the same tables.  XOR blocks of any size are served: rows beyond the LDS go through it in
+ * column slices.  Requests of every kind may alternate on one service.  Thread-safe. */
+int fecgpu_block_svc_rlc_encode_rows(fecgpu_block_svc_t *svc, const uint64_t *src_rows, const uint32_t *src_len,
+                                     const uint64_t *rep_rows, uint32_t blk_len, uint32_t k, uint32_t r,
+                                     uint32_t fbn);
+int fecgpu_block_svc_rlc_decode_rows(fecgpu_block_svc_t *svc, const uint64_t *src_rows, const uint32_t *src_len,
+                                     const uint64_t *rep_rows, const uint32_t *rep_len, uint32_t blk_len, uint32_t k,
+                                     uint32_t r, const uint32_t *rep_seed, const uint64_t *src_present,
+                                     const uint64_t *rep_present, int full, uint8_t *status, uint64_t *recovered);
+int fecgpu_block_svc_xor_encode_rows(fecgpu_block_svc_t *svc, const uint64_t *src_rows, const uint32_t *src_len,
+                                     uint64_t rep_row, uint32_t blk_len, uint32_t k);
+int fecgpu_block_svc_xor_decode_rows(fecgpu_block_svc_t *svc, const uint64_t *src_rows, const uint32_t *src_len,
+                                     uint64_t rep_row, uint32_t blk_len, uint32_t k, const uint64_t *src_present,
+                                     const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
 /* worker generations launched so far (diagnostics: one per idle gap) */
 uint64_t fecgpu_block_svc_launches(const fecgpu_block_svc_t *svc);
 /* A call waits at most `deadline_us` (default 2000) for a worker to take its request.  Past it the

@@ -124,6 +124,29 @@ int pquic_fec_get_recover_mode(void);
  * adapter's completions alike. */
 uint64_t pquic_fec_singular_blocks(void);
 
+/* Where the generate and recover operations (RLC and XOR) find their symbols.  0 (default): every symbol
+ * is copied into page-locked staging rows and every result is copied out of them.  1, in place: a symbol
+ * whose data is 4-byte aligned and lies in page-locked memory the engine knows (fecgpu_host_device_address:
+ * a range registered below or by a batcher, pquic_fec_batch_register_arena) is handed to the engine by its
+ * address and its own data_length, and results are allocated before the engine call and written where
+ * they lie; any other symbol still goes through a staging row, so one block may mix both kinds.  The
+ * block goes to the resident block service's row requests first (XOR included) and, where the service
+ * refuses, through the launch forms on the same tables.  Returns, bytes, lengths, FPIDs, counters and the
+ * recover mode behave as with 0.  Process-wide; takes effect from the next call.  Returns 0, or -1 for
+ * any other value, and for 1 against an engine library without the row requests (the mode then stays as
+ * it was). */
+int pquic_fec_set_hooks_in_place(int on);
+int pquic_fec_get_hooks_in_place(void);
+/* Page-locks [base, base + bytes) -- the allocator's arena -- and makes it known to the engine, for an
+ * integrator who uses the protocol operations without a batcher: thin wrappers over fecgpu_host_register
+ * / fecgpu_host_unregister, 0 or -1.  A range a batcher has registered (pquic_fec_batch_register_arena)
+ * is page-locked already and needs no second registration. */
+int pquic_fec_register_heap(void *base, size_t bytes);
+int pquic_fec_unregister_heap(void *base);
+/* In-place mode's counters: out[0] rows handed over where they lie, out[1] rows that went through a
+ * staging row, out[2] calls the block service's worker served, out[3] calls that took a launch form. */
+void pquic_fec_hook_rows_stats(uint64_t out[4]);
+
 /* packet_payload_to_source_symbol (protoops/packet_payload_to_source_symbol.c:6-36, manifest
  * fec_core.plugin:20): inputs [0] payload bytes, [1] symbol buffer, [2] payload length,
  * [3] packet number; returns the symbol length, PQUIC_ERROR_MEMORY for a NULL buffer, or

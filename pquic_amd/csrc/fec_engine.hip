@@ -2183,6 +2183,69 @@ __device__ __forceinline__ void stage_rows_lds(uint8_t *lrows, const uint8_t *ba
   }
 }
 
+// Row-table entries (the resident worker's row requests; the fused row kernels' format): the row's
+// address in the low 48 bits, the bytes to read from it above.
+constexpr uint64_t kRowAddrMask = (1ull << 48) - 1;
+#define SVC_GLOBAL __attribute__((address_space(1)))
+
+// The length-aware twin of stage_rows_lds: columns [col0, col0 + cw) (multiples of 16) of the rows of
+// table `tab` into LDS rows of `cw` bytes, by threads [t0, kLdsThreads).  Row x is read for min(its
+// entry's bound, B) bytes and counts as zeros past them; with masks, a row whose bit is clear (row x < k:
+// bit x of sp, else bit x - k of rp) is absent.  An absent row and a row of 0 bytes are never
+// dereferenced.  16-B loads where the row's address is 16-B aligned, dwords otherwise; the last load may
+// touch the aligned dword that holds the row's last byte, whose bytes past the bound are masked off.
+__device__ __forceinline__ void stage_rows_tab_lds(uint8_t *lrows, const uint64_t *tab, int nrows, int col0, int cw,
+                                                   int t0, const uint64_t *sp, const uint64_t *rp, int k, int B) {
+  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+  const int tid = (int)threadIdx.x - t0, nt = kLdsThreads - t0;
+  if (tid < 0) return;
+  const int pr = cw >> 4, tot = nrows * pr;
+  for (int x = tid; x < tot; x += nt) {
+    const int row = x / pr, c = x - row * pr, o = col0 + 16 * c;
+    const uint64_t e = tab[row];
+    int n = (int)(e >> 48);
+    if (n > B) n = B;
+    if (sp) {
+      const uint64_t *m = row < k ? sp : rp;
+      const int q = row < k ? row : row - k;
+      if (!((m[q >> 6] >> (q & 63)) & 1)) n = 0;
+    }
+    v4u v = {0u, 0u, 0u, 0u};
+    const int rem = n - o;  // bytes of the row from this piece on
+    if (rem > 0) {
+      const SVC_GLOBAL uint8_t *a = (const SVC_GLOBAL uint8_t *)(e & kRowAddrMask) + o;
+      if (rem > 12 && !((uintptr_t)a & 15)) {
+        v = __builtin_nontemporal_load(reinterpret_cast<const SVC_GLOBAL v4u *>(a));
+      } else {
+#pragma unroll
+        for (int d = 0; d < 4; d++)
+          if (4 * d < rem) v[d] = __builtin_nontemporal_load(reinterpret_cast<const SVC_GLOBAL uint32_t *>(a) + d);
+      }
+      if (rem < 16) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+          const int t = rem - 4 * d;
+          if (t <= 0) v[d] = 0u;
+          else if (t < 4) v[d] &= (1u << (8 * t)) - 1u;
+        }
+      }
+    }
+    *reinterpret_cast<v4u *>(lrows + row * cw + 16 * c) = v;
+  }
+}
+
+// dword w of an output row of B bytes: a dword store, or byte stores for the row's last 1-3 bytes;
+// nothing at or past byte B, and no dword is read-modify-written
+__device__ __forceinline__ void store_word_bounded(uint64_t row, int w, uint32_t v, int B) {
+  SVC_GLOBAL uint32_t *a = (SVC_GLOBAL uint32_t *)(row & kRowAddrMask) + w;
+  const int rem = B - 4 * w;
+  if (rem >= 4) {
+    __builtin_nontemporal_store(v, a);
+  } else {
+    for (int x = 0; x < rem; x++) ((SVC_GLOBAL uint8_t *)a)[x] = (uint8_t)(v >> (8 * x));
+  }
+}
+
 // packed-multiply tables of a tile of OT outputs x k inputs, input-major ([j][o]: the OT tables an
 // input step needs are contiguous, so they load as a few back-to-back broadcast LDS reads); outputs
 // past the tile's live ones get the zero coefficient's (all-zero) tables, so the loops need no guards
@@ -2236,10 +2299,12 @@ struct EncLdsLayout {
 };
 
 // One block's encode with its rows staged in LDS, by all kLdsThreads threads (src_b / rep_b: the
-// block's k source rows and r repair rows, L bytes each).
-template <int RT>
+// block's k source rows and r repair rows, L bytes each).  ROWS: the rows by table instead (tab: k source
+// entries, then r repair entries; L = pad4(B)): every source is read for its own bound, every repair row
+// receives exactly B bytes.
+template <int RT, bool ROWS = false>
 __device__ __forceinline__ void encode_block_lds(uint8_t *lds, const uint8_t *src_b, uint8_t *rep_b, int k, int r,
-                                                 int L, uint32_t f) {
+                                                 int L, uint32_t f, const uint64_t *tab = nullptr, int B = 0) {
   const EncLdsLayout Y(k, r, L, RT);
   const int kpad = (int)pad16((uint32_t)k), Lp = (int)pad16((uint32_t)L), Lw = L >> 2;
   uint8_t *C = lds + Y.coef;
@@ -2253,6 +2318,8 @@ __device__ __forceinline__ void encode_block_lds(uint8_t *lds, const uint8_t *sr
       tmt_init(t, rlc_seed(f, (uint32_t)i));
       for (int j = 0; j < k; j++) C[i * kpad + j] = tmt_coef(t);
     }
+  } else if (ROWS) {
+    stage_rows_tab_lds(lds + Y.rows, tab, k, 0, Lp, 64, nullptr, nullptr, k, B);
   } else {
     stage_rows_lds(lds + Y.rows, src_b, k, L, Lp, 64);
   }
@@ -2264,7 +2331,8 @@ __device__ __forceinline__ void encode_block_lds(uint8_t *lds, const uint8_t *sr
     build_tabs<RT>(T, C, kpad, i0, no, k);
     __syncthreads();
     lds_mac_words<RT>(T, no, k, Lw, rows, Lp >> 2, [&](int i, int w, uint32_t v) {
-      __builtin_nontemporal_store(v, rb + (size_t)(i0 + i) * Lw + w);
+      if (ROWS) store_word_bounded(tab[k + i0 + i], w, v, B);
+      else __builtin_nontemporal_store(v, rb + (size_t)(i0 + i) * Lw + w);
     });
   }
 #ifdef FEC_STAMP
@@ -2306,12 +2374,15 @@ struct DecLdsLayout {
 // up on is planned again from every received repair, a recovered one loses its dependency flags.  The
 // re-plan is compiled in only with FULL (k_block_svc, k_rlc_decode_lds<EM, true>): the kernel of a
 // reference-mode launch keeps its registers (EM 16: 125 VGPRs without it, 143 with it).
-template <int EM, bool FULL>
+// ROWS: the rows by table (tab: k source entries, then r repair entries; L = pad4(B)): a present row is
+// read for its own bound, an absent one is never touched, a block the masks alone leave at NOTHING reads
+// no row at all, and every recovered source goes to the missing source's own entry, exactly B bytes.
+template <int EM, bool FULL, bool ROWS = false>
 __device__ __forceinline__ void decode_block_lds(uint8_t *lds, uint64_t b, const uint8_t *src_b, const uint8_t *rep_b,
                                                  uint8_t *dst_b, int k, int r, int L, uint32_t fbn_base,
                                                  const uint32_t *fbn, const uint32_t *seeds, const uint64_t *sp,
                                                  const uint64_t *rp, uint8_t *status, uint64_t *recovered, int wreg,
-                                                 int full) {
+                                                 int full, const uint64_t *tab = nullptr, int B = 0) {
   const DecLdsLayout Y(k, r, L, EM, FULL && full);
   const WsLayout WL = ws_layout((uint32_t)k, (uint32_t)r);
   const int Lp = (int)pad16((uint32_t)L), Lw = L >> 2;
@@ -2336,6 +2407,13 @@ __device__ __forceinline__ void decode_block_lds(uint8_t *lds, uint64_t b, const
       }
     }
     if (threadIdx.x == 0) *nzword = 0;
+  } else if (ROWS) {  // waves 1-7: the present rows, unless the masks say the block is left alone (as the plan will)
+    uint64_t s0 = sp[2 * b], s1 = sp[2 * b + 1], q0 = rp[2 * b], q1 = rp[2 * b + 1];
+    clip128(s0, s1, k);
+    clip128(q0, q1, r);
+    const int cur_ss = __popcll(s0) + __popcll(s1), cur_rs = __popcll(q0) + __popcll(q1);
+    if (cur_ss != k && cur_ss + cur_rs >= k)
+      stage_rows_tab_lds(lds + Y.rows, tab, k + r, 0, Lp, 64, sp + 2 * b, rp + 2 * b, k, B);
   } else {  // waves 1-7: all k source and r repair rows of the block (absent ones are never read)
     stage_rows_lds(lds + Y.rows, src_b, k, L, Lp, 64);
     stage_rows_lds(lds + Y.rows + k * Lp, rep_b, r, L, Lp, 64);
@@ -2356,7 +2434,8 @@ __device__ __forceinline__ void decode_block_lds(uint8_t *lds, uint64_t b, const
     uint32_t *db = reinterpret_cast<uint32_t *>(dst_b);
     uint32_t nzm = 0;
     lds_mac_words<EM>(T, n, k, Lw, rows, Lq, [&](int u, int w, uint32_t v) {
-      __builtin_nontemporal_store(v, db + (size_t)h[WL.off_unk + u] * Lw + w);
+      if (ROWS) store_word_bounded(tab[h[WL.off_unk + u]], w, v, B);
+      else __builtin_nontemporal_store(v, db + (size_t)h[WL.off_unk + u] * Lw + w);
       nzm |= (uint32_t)(v != 0) << u;
     });
     if (nzm) atomicOr(nzword, nzm);
@@ -2412,8 +2491,23 @@ struct alignas(64) BlockSvcReq {
   uint64_t src, rep, dst;           // device addresses of the block's rows (page-locked host memory)
   uint64_t sp[2], rp[2];            // presence masks (decode)
   uint32_t seeds[kSvcMaxR];         // the repairs' FPID seeds (decode)
+  uint32_t blen;                    // row requests: the block's length in bytes (L = pad4(blen)); in the
+                                    // struct's tail padding, so ops 1-3 keep their bytes and their size
 };
 static_assert(sizeof(BlockSvcReq) % 16 == 0 && sizeof(BlockSvcReq) / 16 <= 64, "one 16-B load per lane of a wave");
+static_assert(sizeof(BlockSvcReq) == 640, "the request of ops 1-3 keeps its size");
+// Row requests (the blocks' rows by address and length): the ops below take their rows from the
+// mailbox's row table -- the k source entries, then the repair entries (kRowAddrMask format) -- and
+// src / rep / dst are unused.
+enum : uint32_t {
+  kSvcOpEncRows = 4,     // RLC encode
+  kSvcOpDecRows = 5,     // RLC decode with per-repair seeds
+  kSvcOpDecRowsFull = 6, // the same, full rank
+  kSvcOpXorEncRows = 7,  // XOR encode (one repair entry)
+  kSvcOpXorDecRows = 8,  // XOR decode (one repair entry)
+};
+constexpr int kSvcRowEntries = FECGPU_MAX_K + kSvcMaxR;
+constexpr uint32_t kSvcLds = 60 * 1024;  // dynamic LDS of the worker (the mailbox copies are static)
 struct alignas(64) BlockSvcMailbox {
   BlockSvcReq req;
   uint64_t done;                    // device: last request number finished (release)
@@ -2422,7 +2516,53 @@ struct alignas(64) BlockSvcMailbox {
   uint64_t quit;                    // host: 1 = end the worker
   uint64_t launches;                // device: worker generations started (diagnostics)
   uint64_t stamp[4];                // device: claim, request in LDS, rows coded, before done (s_memrealtime)
+  alignas(64) uint64_t rows[kSvcRowEntries];  // host: the row table of a row request (written before req.seq)
 };
+static_assert(sizeof(uint64_t) * kSvcRowEntries / 16 <= kLdsThreads - 64, "one 16-B load per lane of waves 1 and up");
+
+__device__ __forceinline__ int xor_rows_status(const uint64_t *sp, const uint64_t *rp, uint64_t b, int k, int *miss);
+
+// One XOR block of a row request, by all kLdsThreads threads: the input rows -- encode: the k sources;
+// decode: the present sources and the repair (table entry k) -- are staged like the RLC rows, each for
+// its own bound, then every output dword is one XOR reduction down the LDS rows and goes out through
+// the bounded store: exactly B bytes to the repair row (encode) or to the missing source's own entry
+// (decode).  Blocks whose rows exceed the LDS go through it in column slices, one round trip each.
+// Decode: status and the recovered bit by xor_rows_status (as fecgpu_xor_decode_rows); a block that is
+// not RECOVERED reads and writes no row.
+template <bool DEC>
+__device__ __forceinline__ void xor_block_lds(uint8_t *lds, const uint64_t *tab, int k, int L, int B,
+                                              const uint64_t *sp, const uint64_t *rp, uint8_t *status,
+                                              uint64_t *recovered) {
+  int miss = -1, st = FECGPU_BLOCK_RECOVERED;
+  if (DEC) {
+    st = xor_rows_status(sp, rp, 0, k, &miss);
+    if (threadIdx.x == 0) {
+      status[0] = (uint8_t)st;
+      recovered[0] = miss >= 0 && miss < 64 ? 1ull << miss : 0;
+      recovered[1] = miss >= 64 ? 1ull << (miss - 64) : 0;
+    }
+    if (st != FECGPU_BLOCK_RECOVERED) return;
+  }
+  const int nin = DEC ? k + 1 : k, Lp = (int)pad16((uint32_t)L);
+  const uint64_t out = DEC ? tab[miss] : tab[k];
+  int cw = (int)((kSvcLds / (uint32_t)nin) & ~15u);  // bytes of every row one slice holds
+  if (cw > Lp) cw = Lp;
+  const uint32_t *rows = reinterpret_cast<const uint32_t *>(lds);
+  for (int col0 = 0; col0 < Lp; col0 += cw) {
+    const int w = Lp - col0 < cw ? Lp - col0 : cw;
+    __syncthreads();  // the previous slice's reads
+    stage_rows_tab_lds(lds, tab, nin, col0, w, 0, DEC ? sp : nullptr, rp, k, B);
+    __syncthreads();
+    for (int x = threadIdx.x; x < (w >> 2); x += kLdsThreads) {
+      const int word = (col0 >> 2) + x;
+      if (4 * word >= B) continue;
+      uint32_t acc = 0;
+#pragma unroll 4
+      for (int j = 0; j < nin; j++) acc ^= rows[j * (w >> 2) + x];
+      store_word_bounded(out, word, acc, B);
+    }
+  }
+}
 
 __device__ __forceinline__ uint64_t sys_load(const uint64_t *p) {
   return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -2432,6 +2572,7 @@ __global__ __launch_bounds__(kLdsThreads) void k_block_svc(BlockSvcMailbox *mb, 
                                                            uint64_t life_ticks) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   __shared__ BlockSvcReq R;
+  __shared__ __attribute__((aligned(16))) uint64_t RT[kSvcRowEntries];  // the row table of a row request
   __shared__ int go;
   const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
   uint64_t t_last = t_start, done = 0;
@@ -2470,6 +2611,12 @@ __global__ __launch_bounds__(kLdsThreads) void k_block_svc(BlockSvcMailbox *mb, 
       typedef uint32_t v4u __attribute__((ext_vector_type(4)));
       reinterpret_cast<v4u *>(&R)[threadIdx.x] =
           __builtin_nontemporal_load(reinterpret_cast<const v4u *>(&mb->req) + threadIdx.x);
+    } else if (threadIdx.x >= 64 && threadIdx.x - 64 < sizeof(RT) / 16) {
+      // the row table in the same round trip, before the op is known: a row request's loads then wait
+      // for nothing more, and ops 1-3 ignore it
+      typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+      reinterpret_cast<v4u *>(RT)[threadIdx.x - 64] =
+          __builtin_nontemporal_load(reinterpret_cast<const v4u *>(mb->rows) + (threadIdx.x - 64));
     }
     __syncthreads();
     if (threadIdx.x == 0)
@@ -2481,6 +2628,23 @@ __global__ __launch_bounds__(kLdsThreads) void k_block_svc(BlockSvcMailbox *mb, 
       if (r <= 4) encode_block_lds<4>(lds, src, rep, k, r, L, R.fbn);
       else if (r <= 8) encode_block_lds<8>(lds, src, rep, k, r, L, R.fbn);
       else encode_block_lds<16>(lds, src, rep, k, r, L, R.fbn);
+    } else if (R.op == kSvcOpEncRows) {
+      const int B = (int)R.blen;
+      if (r <= 4) encode_block_lds<4, true>(lds, nullptr, nullptr, k, r, L, R.fbn, RT, B);
+      else if (r <= 8) encode_block_lds<8, true>(lds, nullptr, nullptr, k, r, L, R.fbn, RT, B);
+      else encode_block_lds<16, true>(lds, nullptr, nullptr, k, r, L, R.fbn, RT, B);
+    } else if (R.op == kSvcOpDecRows || R.op == kSvcOpDecRowsFull) {
+      uint8_t *st = reinterpret_cast<uint8_t *>(&mb->status);
+      uint64_t *rec = mb->recovered;
+      const int full = R.op == kSvcOpDecRowsFull, B = (int)R.blen;
+      if (em <= 4) decode_block_lds<4, true, true>(lds, 0, nullptr, nullptr, nullptr, k, r, L, 0, nullptr, R.seeds, R.sp, R.rp, st, rec, R.wreg, full, RT, B);
+      else if (em <= 8) decode_block_lds<8, true, true>(lds, 0, nullptr, nullptr, nullptr, k, r, L, 0, nullptr, R.seeds, R.sp, R.rp, st, rec, R.wreg, full, RT, B);
+      else decode_block_lds<16, true, true>(lds, 0, nullptr, nullptr, nullptr, k, r, L, 0, nullptr, R.seeds, R.sp, R.rp, st, rec, R.wreg, full, RT, B);
+    } else if (R.op == kSvcOpXorEncRows) {
+      xor_block_lds<false>(lds, RT, k, L, (int)R.blen, nullptr, nullptr, nullptr, nullptr);
+    } else if (R.op == kSvcOpXorDecRows) {
+      xor_block_lds<true>(lds, RT, k, L, (int)R.blen, R.sp, R.rp, reinterpret_cast<uint8_t *>(&mb->status),
+                          mb->recovered);
     } else {
       const uint8_t *src = (const uint8_t *)R.src, *rep = (const uint8_t *)R.rep;
       uint8_t *dst = (uint8_t *)R.dst;
@@ -4810,7 +4974,6 @@ constexpr uint64_t kSvcBackoffUs = 50000;
 // it share one, kernels queued behind the resident worker wait at most its lifetime (sustained hook
 // traffic then pays one relaunch per 50 ms).
 constexpr uint64_t kSvcIdleTicks = 2000000, kSvcLifeTicks = 5000000;
-constexpr uint32_t kSvcLds = 60 * 1024;  // dynamic LDS of the worker (the mailbox copy is static)
 
 fecgpu_block_svc_t *fecgpu_block_svc_create(int device) {
   if (fecgpu_init(device) != FECGPU_OK) return nullptr;
@@ -5043,6 +5206,139 @@ int fecgpu_block_svc_rlc_decode_full(fecgpu_block_svc_t *v, const void *src, con
                                      const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
                                      uint64_t *recovered) {
   return svc_decode(v, src, rep, dst, k, r, symbol_size, rep_seed, src_present, rep_present, status, recovered, 3);
+}
+
+// ---- row requests: every row by address and length ----
+// Shapes of a row request (r: the repair entries, 1 for XOR).
+static int svc_rows_shape(uint32_t k, uint32_t r, uint32_t blk_len) {
+  if (k < 1 || k > FECGPU_MAX_K) return set_err(FECGPU_ERR_INVALID, "%s", "k out of range [1,128]");
+  if (r < 1 || r > FECGPU_MAX_R || r > (uint32_t)kSvcMaxR)
+    return set_err(FECGPU_ERR_INVALID, "%s", "block service: r out of range [1,128]");
+  if (blk_len < 1 || blk_len > 65532) return set_err(FECGPU_ERR_INVALID, "%s", "block service: blk_len out of range [1,65532]");
+  return FECGPU_OK;
+}
+
+// One table entry: `n` bytes are read at `addr` (0: the row is not read); deref: the row is read or written.
+static int svc_row_entry(uint64_t addr, uint32_t n, bool deref, uint64_t *e) {
+  if (deref && ((addr & 3) || (addr >> 48)))
+    return set_err(FECGPU_ERR_INVALID, "%s", "block service: row addresses must be 4-byte aligned and below 2^48");
+  *e = deref ? (addr & kRowAddrMask) | ((uint64_t)n << 48) : 0;
+  return FECGPU_OK;
+}
+
+static bool svc_bit(const uint64_t *m, uint32_t x) { return (m[x >> 6] >> (x & 63)) & 1; }
+
+// Posts a row request: the table (nrows entries, checked) into the mailbox, then the request.
+static int svc_post_rows(fecgpu_block_svc_t *v, uint32_t op, const uint64_t *tab, uint32_t nrows, uint32_t k, uint32_t r,
+                         uint32_t blk_len, uint32_t fbn, const uint32_t *rep_seed, const uint64_t *sp,
+                         const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+  std::lock_guard<std::mutex> g(v->mu);
+  int cur = 0;
+  HIPCHK(hipGetDevice(&cur));
+  if (cur != v->device) HIPCHK(hipSetDevice(v->device));
+  BlockSvcReq *m = &v->mb->req;
+  m->op = op; m->k = k; m->r = r; m->L = (blk_len + 3u) & ~3u; m->blen = blk_len; m->fbn = fbn & 0xffffffu;
+  m->wreg = knob(K_PLAN) != PLAN_WAVE;
+  if (sp) {
+    m->sp[0] = sp[0]; m->sp[1] = sp[1];
+    m->rp[0] = rp[0]; m->rp[1] = rp[1];
+  }
+  if (rep_seed) memcpy(m->seeds, rep_seed, (size_t)r * 4);
+  memcpy(v->mb->rows, tab, (size_t)nrows * 8);
+  const int rc = svc_run(v);
+  if (cur != v->device) (void)hipSetDevice(cur);
+  if (!rc) {
+    if (status) {
+      *status = (uint8_t)v->mb->status;
+      recovered[0] = v->mb->recovered[0];
+      recovered[1] = v->mb->recovered[1];
+      count_decode(1);
+    } else {
+      count_encode(1);
+    }
+  }
+  return rc;
+}
+
+int fecgpu_block_svc_rlc_encode_rows(fecgpu_block_svc_t *v, const uint64_t *src_rows, const uint32_t *src_len,
+                                     const uint64_t *rep_rows, uint32_t blk_len, uint32_t k, uint32_t r,
+                                     uint32_t fbn) {
+  if (!v || !knob(K_BLOCK_SVC)) return FECGPU_ERR_INVALID;
+  if (!src_rows || !src_len || !rep_rows) return set_err(FECGPU_ERR_INVALID, "%s", "block service: NULL table");
+  if (int rc = svc_rows_shape(k, r, blk_len)) return rc;
+  const uint32_t L = (blk_len + 3u) & ~3u;
+  if (EncLdsLayout((int)k, (int)r, (int)L, r <= 4 ? 4 : r <= 8 ? 8 : 16).bytes > kSvcLds)
+    return set_err(FECGPU_ERR_INVALID, "%s", "block service: block too large for its LDS");
+  uint64_t tab[kSvcRowEntries];
+  for (uint32_t j = 0; j < k; j++) {
+    if (src_len[j] > blk_len) return set_err(FECGPU_ERR_INVALID, "%s", "block service: src_len exceeds blk_len");
+    if (int rc = svc_row_entry(src_rows[j], src_len[j], src_len[j] != 0, &tab[j])) return rc;
+  }
+  for (uint32_t i = 0; i < r; i++)
+    if (int rc = svc_row_entry(rep_rows[i], 0, true, &tab[k + i])) return rc;
+  return svc_post_rows(v, kSvcOpEncRows, tab, k + r, k, r, blk_len, fbn, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int fecgpu_block_svc_rlc_decode_rows(fecgpu_block_svc_t *v, const uint64_t *src_rows, const uint32_t *src_len,
+                                     const uint64_t *rep_rows, const uint32_t *rep_len, uint32_t blk_len, uint32_t k,
+                                     uint32_t r, const uint32_t *rep_seed, const uint64_t *src_present,
+                                     const uint64_t *rep_present, int full, uint8_t *status, uint64_t *recovered) {
+  if (!v || !knob(K_BLOCK_SVC)) return FECGPU_ERR_INVALID;
+  if (!src_rows || !src_len || !rep_rows || !rep_len || !rep_seed || !src_present || !rep_present || !status ||
+      !recovered)
+    return set_err(FECGPU_ERR_INVALID, "%s", "block service: NULL argument");
+  if (int rc = svc_rows_shape(k, r, blk_len)) return rc;
+  const uint32_t L = (blk_len + 3u) & ~3u, em = k < r ? k : r;
+  if (em > 16 || knob(K_PLAN) != 0 ||
+      DecLdsLayout((int)k, (int)r, (int)L, em <= 4 ? 4 : em <= 8 ? 8 : 16, full != 0).bytes > kSvcLds)
+    return set_err(FECGPU_ERR_INVALID, "%s", "block service: block too large for its LDS");
+  uint64_t tab[kSvcRowEntries];
+  for (uint32_t j = 0; j < k; j++) {
+    // a received source is read for min(its length, blk_len) bytes (the reference truncates a symbol
+    // longer than the block); a missing one is the row its recovered bytes go to
+    const bool have = svc_bit(src_present, j);
+    const uint32_t n = !have ? 0 : src_len[j] < blk_len ? src_len[j] : blk_len;
+    if (int rc = svc_row_entry(src_rows[j], n, !have || n != 0, &tab[j])) return rc;
+  }
+  for (uint32_t i = 0; i < r; i++) {
+    const uint32_t n = !svc_bit(rep_present, i) ? 0 : rep_len[i] < blk_len ? rep_len[i] : blk_len;
+    if (int rc = svc_row_entry(rep_rows[i], n, n != 0, &tab[k + i])) return rc;
+  }
+  return svc_post_rows(v, full ? kSvcOpDecRowsFull : kSvcOpDecRows, tab, k + r, k, r, blk_len, 0, rep_seed, src_present,
+                       rep_present, status, recovered);
+}
+
+int fecgpu_block_svc_xor_encode_rows(fecgpu_block_svc_t *v, const uint64_t *src_rows, const uint32_t *src_len,
+                                     uint64_t rep_row, uint32_t blk_len, uint32_t k) {
+  if (!v || !knob(K_BLOCK_SVC)) return FECGPU_ERR_INVALID;
+  if (!src_rows || !src_len) return set_err(FECGPU_ERR_INVALID, "%s", "block service: NULL table");
+  if (int rc = svc_rows_shape(k, 1, blk_len)) return rc;
+  uint64_t tab[kSvcRowEntries];
+  for (uint32_t j = 0; j < k; j++) {
+    if (src_len[j] > blk_len) return set_err(FECGPU_ERR_INVALID, "%s", "block service: src_len exceeds blk_len");
+    if (int rc = svc_row_entry(src_rows[j], src_len[j], src_len[j] != 0, &tab[j])) return rc;
+  }
+  if (int rc = svc_row_entry(rep_row, 0, true, &tab[k])) return rc;
+  return svc_post_rows(v, kSvcOpXorEncRows, tab, k + 1, k, 1, blk_len, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int fecgpu_block_svc_xor_decode_rows(fecgpu_block_svc_t *v, const uint64_t *src_rows, const uint32_t *src_len,
+                                     uint64_t rep_row, uint32_t blk_len, uint32_t k, const uint64_t *src_present,
+                                     const uint64_t *rep_present, uint8_t *status, uint64_t *recovered) {
+  if (!v || !knob(K_BLOCK_SVC)) return FECGPU_ERR_INVALID;
+  if (!src_rows || !src_len || !src_present || !rep_present || !status || !recovered)
+    return set_err(FECGPU_ERR_INVALID, "%s", "block service: NULL argument");
+  if (int rc = svc_rows_shape(k, 1, blk_len)) return rc;
+  uint64_t tab[kSvcRowEntries];
+  for (uint32_t j = 0; j < k; j++) {
+    const bool have = svc_bit(src_present, j);
+    const uint32_t n = !have ? 0 : src_len[j] < blk_len ? src_len[j] : blk_len;
+    if (int rc = svc_row_entry(src_rows[j], n, !have || n != 0, &tab[j])) return rc;
+  }
+  const bool rep = rep_present[0] & 1;
+  if (int rc = svc_row_entry(rep_row, rep ? blk_len : 0, rep, &tab[k])) return rc;
+  return svc_post_rows(v, kSvcOpXorDecRows, tab, k + 1, k, 1, blk_len, 0, nullptr, src_present, rep_present, status,
+                       recovered);
 }
 
 uint64_t fecgpu_block_svc_launches(const fecgpu_block_svc_t *v) {

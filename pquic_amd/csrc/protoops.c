@@ -5,7 +5,9 @@
  * Each operation reads the fec_block_t the framework passes in, stages its symbols into a
  * zero-padded fixed-size row layout, runs the device engine through the host-resident
  * entry points of include/fecgpu.h (one block per call, synchronous like the reference),
- * and writes results back into the block with the caller's allocator.  The arithmetic
+ * and writes results back into the block with the caller's allocator.  With
+ * pquic_fec_set_hooks_in_place(1) the symbols that lie in page-locked memory are handed over by address
+ * instead and the results are written where they lie (the in-place mode below).  The arithmetic
  * itself never runs on the CPU: if no gfx950 device is usable the operation fails with an
  * error code instead of computing.
  */
@@ -42,6 +44,19 @@ static int g_device;
 #pragma weak fecgpu_block_svc_rlc_decode_full
 #pragma weak fecgpu_rlc_decode_host_full
 static int g_recover_mode; /* 0 reference, 1 full rank (pquic_fec_set_recover_mode), under g_mu */
+/* In-place mode is optional in the same way: it needs the block service's row requests and the launch
+ * forms on row tables they fall back to. */
+#pragma weak fecgpu_block_svc_rlc_encode_rows
+#pragma weak fecgpu_block_svc_rlc_decode_rows
+#pragma weak fecgpu_block_svc_xor_encode_rows
+#pragma weak fecgpu_block_svc_xor_decode_rows
+#pragma weak fecgpu_rlc_encode_rows_fused_host
+#pragma weak fecgpu_rlc_decode_rows_fused_host
+#pragma weak fecgpu_rlc_decode_rows_fused_host_full
+#pragma weak fecgpu_xor_encode_rows_host
+#pragma weak fecgpu_xor_decode_rows_host
+static int g_in_place;          /* pquic_fec_set_hooks_in_place, under g_mu */
+static uint64_t g_row_stats[4]; /* rows in place, rows staged, calls the worker served, calls launched; under g_mu */
 static fecgpu_host_ctx_t *g_ctx;
 /* the resident single-block service (fecgpu_block_svc_*): one block per call without a kernel launch;
  * calls it refuses (block too large for it, knob off) take the host path */
@@ -101,6 +116,39 @@ int pquic_fec_get_recover_mode(void) {
 }
 
 uint64_t pquic_fec_singular_blocks(void) { return __atomic_load_n(&g_fec_singular_blocks, __ATOMIC_RELAXED); }
+
+int pquic_fec_set_hooks_in_place(int on) {
+    if (on != 0 && on != 1) return -1;
+    if (on && (fecgpu_block_svc_rlc_encode_rows == NULL || fecgpu_block_svc_rlc_decode_rows == NULL ||
+               fecgpu_block_svc_xor_encode_rows == NULL || fecgpu_block_svc_xor_decode_rows == NULL ||
+               fecgpu_rlc_encode_rows_fused_host == NULL || fecgpu_rlc_decode_rows_fused_host == NULL ||
+               fecgpu_rlc_decode_rows_fused_host_full == NULL || fecgpu_xor_encode_rows_host == NULL ||
+               fecgpu_xor_decode_rows_host == NULL))
+        return -1;
+    pthread_mutex_lock(&g_mu);
+    g_in_place = on;
+    pthread_mutex_unlock(&g_mu);
+    return 0;
+}
+
+int pquic_fec_get_hooks_in_place(void) {
+    pthread_mutex_lock(&g_mu);
+    const int on = g_in_place;
+    pthread_mutex_unlock(&g_mu);
+    return on;
+}
+
+int pquic_fec_register_heap(void *base, size_t bytes) {
+    return base && bytes && fecgpu_host_register(base, bytes) == FECGPU_OK ? 0 : -1;
+}
+
+int pquic_fec_unregister_heap(void *base) { return base && fecgpu_host_unregister(base) == FECGPU_OK ? 0 : -1; }
+
+void pquic_fec_hook_rows_stats(uint64_t out[4]) {
+    pthread_mutex_lock(&g_mu);
+    memcpy(out, g_row_stats, sizeof g_row_stats);
+    pthread_mutex_unlock(&g_mu);
+}
 
 void pquic_fec_protoop_stats(pquic_fec_protoop_stats_t *out) {
     out->generate_calls = __atomic_load_n(&g_fec_stats.generate_calls, __ATOMIC_RELAXED);
@@ -189,6 +237,180 @@ protoop_arg_t pquic_fec_xor_create_fec_schemes(picoquic_cnx_t *cnx) {
     return 0;
 }
 
+/* ------------------------------------------------------------------ in-place mode */
+
+/* The row tables of one block (under g_mu).  A symbol whose data is 4-byte aligned and lies in page-locked
+ * memory the engine knows is entered by its own address; any other goes through its row of g_src / g_rep
+ * (stride L), which are page-locked. */
+typedef struct {
+    uint64_t src[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK], rep[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK];
+    uint32_t src_len[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK], rep_len[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK];
+    uint64_t src_dev, rep_dev; /* device addresses of g_src / g_rep */
+    uint32_t L;
+} rows_t;
+static rows_t g_rows;
+
+static int rows_begin(rows_t *t, int k, int r, uint32_t L) {
+    if (stage((size_t)k * L, (size_t)r * L)) return -1;
+    if (fecgpu_host_device_address(g_src, (size_t)k * L, &t->src_dev) != FECGPU_OK ||
+        fecgpu_host_device_address(g_rep, (size_t)r * L, &t->rep_dev) != FECGPU_OK)
+        return -1;
+    t->L = L;
+    return 0;
+}
+
+/* The address that stands for `n` bytes at `data`: their own when they can be used where they lie (1 into
+ * *in_place), else that of staging row `stage_dev` (0). */
+static uint64_t row_address(const void *data, uint32_t n, uint64_t stage_dev, int *in_place) {
+    uint64_t d = 0;
+    *in_place = n && !((uintptr_t)data & 3) && fecgpu_host_device_address(data, n, &d) == FECGPU_OK;
+    g_row_stats[*in_place ? 0 : 1]++;
+    return *in_place ? d : stage_dev;
+}
+
+/* an input row: n bytes of `data` (copied into its staging row unless they are used in place) */
+static uint64_t row_input(const void *data, uint32_t n, uint8_t *stage_row, uint64_t stage_dev) {
+    int in_place;
+    if (!n) return 0; /* never dereferenced */
+    const uint64_t a = row_address(data, n, stage_dev, &in_place);
+    if (!in_place) memcpy(stage_row, data, n);
+    return a;
+}
+
+static void row_call_done(int served) { g_row_stats[served ? 2 : 3]++; }
+
+/* generate with the mode on (maxl > 0; under g_mu): the repairs are allocated first, in the order
+ * fec_generate_finish allocates them, and the engine writes them where they lie */
+static protoop_arg_t generate_in_place(picoquic_cnx_t *cnx, pquic_fec_block_t *fb, int xor_scheme, uint16_t maxl) {
+    const int k = fb->total_source_symbols, r = fb->total_repair_symbols;
+    const uint32_t fbn = fb->fec_block_number & 0xffffffu, blk = maxl, L = fec_pad4(maxl);
+    rows_t *t = &g_rows;
+    fecgpu_host_ctx_t *c = rows_begin(t, k, r, L) ? NULL : ctx();
+    if (!c) {
+        FEC_STAT_ADD(errors, 1);
+        return PQUIC_FEC_ERR_UNBOUND;
+    }
+    pquic_repair_symbol_t *reps[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK];
+    const int n = fec_generate_alloc(cnx, fb, maxl, reps);
+    uint64_t copy[2] = {0, 0};
+    int rc = 0;
+    if (n) { /* the first n repairs do not depend on the later ones */
+        for (int j = 0; j < k; j++) {
+            const pquic_source_symbol_t *ss = fb->source_symbols[j];
+            t->src_len[j] = ss ? ss->data_length : 0;
+            t->src[j] = row_input(ss ? ss->data : NULL, t->src_len[j], g_src + (size_t)j * L, t->src_dev + (uint64_t)j * L);
+        }
+        for (int i = 0; i < n; i++) {
+            int in_place;
+            t->rep[i] = row_address(reps[i]->data, blk, t->rep_dev + (uint64_t)i * L, &in_place);
+            if (!in_place) copy[i >> 6] |= 1ull << (i & 63);
+        }
+        fecgpu_block_svc_t *v = svc();
+        if (!v)
+            rc = FECGPU_ERR_INVALID;
+        else if (xor_scheme)
+            rc = fecgpu_block_svc_xor_encode_rows(v, t->src, t->src_len, t->rep[0], blk, (uint32_t)k);
+        else
+            rc = fecgpu_block_svc_rlc_encode_rows(v, t->src, t->src_len, t->rep, blk, (uint32_t)k, (uint32_t)n, fbn);
+        const int served = rc == FECGPU_OK;
+        if (rc == FECGPU_ERR_INVALID)
+            rc = xor_scheme ? fecgpu_xor_encode_rows_host(c, t->src, t->src_len, t->rep, &blk, 1, (uint32_t)k, L)
+                            : fecgpu_rlc_encode_rows_fused_host(c, t->src, t->src_len, t->rep, &blk, 1, (uint32_t)k,
+                                                                (uint32_t)n, L, &fbn);
+        if (!rc) row_call_done(served);
+    }
+    if (rc) {
+        for (int i = 0; i < n; i++) {
+            g_fec_api.my_free(cnx, reps[i]->data);
+            g_fec_api.my_free(cnx, reps[i]);
+        }
+        FEC_STAT_ADD(errors, 1);
+        return PQUIC_FEC_ERR_UNBOUND;
+    }
+    for (int i = 0; i < n; i++)
+        if ((copy[i >> 6] >> (i & 63)) & 1) memcpy(reps[i]->data, g_rep + (size_t)i * L, maxl);
+    return fec_generate_attach(fb, reps, n);
+}
+
+/* recover with the mode on (maxl > 0; under g_mu): the symbols a recovery would insert are allocated
+ * first (fec_recover_alloc / _alloc_xor, as the batcher does) and the engine writes them where they lie */
+static protoop_arg_t recover_in_place(picoquic_cnx_t *cnx, pquic_fec_block_t *fb, int xor_scheme, uint16_t maxl) {
+    const int k = fb->total_source_symbols, r = xor_scheme ? 1 : fb->total_repair_symbols;
+    const uint32_t blk = maxl, L = fec_pad4(maxl);
+    rows_t *t = &g_rows;
+    fecgpu_host_ctx_t *c = rows_begin(t, k, r, L) ? NULL : ctx();
+    if (!c) {
+        FEC_STAT_ADD(errors, 1);
+        return PQUIC_FEC_ERR_UNBOUND;
+    }
+    pquic_source_symbol_t *pre[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK];
+    if (xor_scheme) fec_recover_alloc_xor(cnx, fb, maxl, pre);
+    else fec_recover_alloc(cnx, fb, maxl, pre);
+    uint32_t seeds[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK];
+    uint64_t sp[2] = {0, 0}, rp[2] = {0, 0}, copy[2] = {0, 0}, rec[2] = {0, 0};
+    uint8_t st = FECGPU_BLOCK_NOTHING;
+    for (int j = 0; j < k; j++) {
+        const pquic_source_symbol_t *ss = fb->source_symbols[j];
+        uint8_t *row = g_src + (size_t)j * L;
+        const uint64_t row_dev = t->src_dev + (uint64_t)j * L;
+        if (ss) { /* bytes past max_length are never read back (:205): truncate */
+            t->src_len[j] = ss->data_length < maxl ? ss->data_length : maxl;
+            t->src[j] = row_input(ss->data, t->src_len[j], row, row_dev);
+            sp[j >> 6] |= 1ull << (j & 63);
+            continue;
+        }
+        /* a missing source: the row its recovered bytes go to -- the symbol allocated for it, or its staging
+         * row when that is not page-locked or was not allocated (fec_recover_finish_pre copies it out) */
+        int in_place = 0;
+        t->src_len[j] = 0;
+        t->src[j] = pre[j] ? row_address(pre[j]->data, blk, row_dev, &in_place) : row_dev;
+        if (!in_place) copy[j >> 6] |= 1ull << (j & 63);
+    }
+    for (int i = 0; i < r; i++) {
+        const pquic_repair_symbol_t *rs = fb->repair_symbols[i];
+        t->rep_len[i] = !rs ? 0 : rs->data_length < maxl ? rs->data_length : maxl;
+        t->rep[i] = rs ? row_input(rs->data, t->rep_len[i], g_rep + (size_t)i * L, t->rep_dev + (uint64_t)i * L) : 0;
+        if (rs) rp[i >> 6] |= 1ull << (i & 63);
+        seeds[i] = rs ? rs->fpid.f.source_fpid.raw : 0; /* the repair's own FPID (:200), see fec_recover_stage */
+    }
+    const int full = !xor_scheme && g_recover_mode == 1;
+    fecgpu_block_svc_t *v = svc();
+    int rc;
+    if (!v)
+        rc = FECGPU_ERR_INVALID;
+    else if (xor_scheme)
+        rc = fecgpu_block_svc_xor_decode_rows(v, t->src, t->src_len, t->rep[0], blk, (uint32_t)k, sp, rp, &st, rec);
+    else
+        rc = fecgpu_block_svc_rlc_decode_rows(v, t->src, t->src_len, t->rep, t->rep_len, blk, (uint32_t)k, (uint32_t)r,
+                                              seeds, sp, rp, full, &st, rec);
+    const int served = rc == FECGPU_OK;
+    if (rc == FECGPU_ERR_INVALID) {
+        if (xor_scheme)
+            rc = fecgpu_xor_decode_rows_host(c, t->src, t->src_len, t->rep, &blk, 1, (uint32_t)k, L, sp, rp, &st, rec);
+        else if (full)
+            rc = fecgpu_rlc_decode_rows_fused_host_full(c, t->src, t->src_len, t->rep, t->rep_len, &blk, 1, (uint32_t)k,
+                                                        (uint32_t)r, L, seeds, sp, rp, &st, rec);
+        else
+            rc = fecgpu_rlc_decode_rows_fused_host(c, t->src, t->src_len, t->rep, t->rep_len, &blk, 1, (uint32_t)k,
+                                                   (uint32_t)r, L, seeds, sp, rp, &st, rec);
+    }
+    if (rc) {
+        for (int j = 0; j < k; j++)
+            if (pre[j]) {
+                g_fec_api.my_free(cnx, pre[j]->data);
+                g_fec_api.my_free(cnx, pre[j]);
+            }
+        FEC_STAT_ADD(errors, 1);
+        return PQUIC_FEC_ERR_UNBOUND;
+    }
+    row_call_done(served);
+    uint64_t nrec = 0;
+    const protoop_arg_t ret = xor_scheme ? fec_recover_finish_pre_xor(cnx, fb, st, rec, pre, copy, g_src, L, maxl, &nrec)
+                                         : fec_recover_finish_pre(cnx, fb, st, rec, pre, copy, g_src, L, maxl, &nrec);
+    if (nrec) FEC_STAT_ADD(recovered_symbols, nrec);
+    return ret;
+}
+
 /* ------------------------------------------------------------------ generate */
 
 static protoop_arg_t generate(picoquic_cnx_t *cnx, int xor_scheme) {
@@ -205,6 +427,11 @@ static protoop_arg_t generate(picoquic_cnx_t *cnx, int xor_scheme) {
     const uint32_t fbn = fb->fec_block_number & 0xffffffu;
     pthread_mutex_lock(&g_mu);
     FEC_STAT_ADD(generate_calls, 1);
+    if (g_in_place && maxl) { /* (a block of empty symbols has no row to hand over: staged) */
+        const protoop_arg_t ret = generate_in_place(cnx, fb, xor_scheme, maxl);
+        pthread_mutex_unlock(&g_mu);
+        return ret;
+    }
     const uint32_t L = fec_pad4(maxl ? maxl : 1);
     int rc = stage((size_t)k * L, (size_t)r * L);
     fecgpu_host_ctx_t *c = rc ? NULL : ctx();
@@ -251,6 +478,11 @@ static protoop_arg_t recover(picoquic_cnx_t *cnx, int xor_scheme) {
     const int k = fb->total_source_symbols, r = xor_scheme ? 1 : fb->total_repair_symbols;
     pthread_mutex_lock(&g_mu);
     FEC_STAT_ADD(recover_calls, 1);
+    if (g_in_place && maxl) {
+        const protoop_arg_t ret = recover_in_place(cnx, fb, xor_scheme, maxl);
+        pthread_mutex_unlock(&g_mu);
+        return ret;
+    }
     const uint32_t L = fec_pad4(maxl ? maxl : 1);
     int rc = stage((size_t)k * L, (size_t)r * L);
     fecgpu_host_ctx_t *c = rc ? NULL : ctx();

@@ -130,6 +130,11 @@ def load_library(path: str = LIB_PATH, private: bool = False):
         L.fecgpu_rlc_window_rows_workspace.restype = sz
         L.fecgpu_rlc_window_encode_rows.argtypes = [v, v, u64, v, v, v, u64, u32, u32, u32, v, sz, v]
         L.fecgpu_rlc_window_encode_rows_host.argtypes = [v, v, v, u64, v, v, v, u64, u32, u32, u32]
+    if hasattr(L, "fecgpu_block_svc_rlc_encode_rows"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
+        L.fecgpu_block_svc_rlc_encode_rows.argtypes = [v, v, v, v, u32, u32, u32, u32]
+        L.fecgpu_block_svc_rlc_decode_rows.argtypes = [v, v, v, v, v, u32, u32, u32, v, v, v, C.c_int, v, v]
+        L.fecgpu_block_svc_xor_encode_rows.argtypes = [v, v, v, u64, u32, u32]
+        L.fecgpu_block_svc_xor_decode_rows.argtypes = [v, v, v, u64, u32, u32, v, v, v, v]
     if hasattr(L, "fecgpu_rlc_window_encode_table"):
         L.fecgpu_rlc_window_encode_table.argtypes = [v, u64, v, u64, u32, u32, u32, v, v]
     if not private:

@@ -833,14 +833,34 @@ long bl_hook_calls(uint64_t *out, long max) {
     return n;
 }
 
-int bl_hook_latency(int device, int k, int r, int L, int e, long ncalls, double out[7]) {
+/* The in-place mode of the hooks is optional: this load generator also runs against an engine library
+ * built from an earlier commit (A/B baselines), which lacks it. */
+#pragma weak pquic_fec_set_hooks_in_place
+#pragma weak pquic_fec_register_heap
+#pragma weak pquic_fec_unregister_heap
+#pragma weak pquic_fec_hook_rows_stats
+
+/* xor_scheme: the XOR hooks (r and e must be 1).  arena: the sources and every symbol the hooks allocate
+ * lie in one arena registered with the engine (pquic_fec_register_heap) instead of on the heap.
+ * in_place: pquic_fec_set_hooks_in_place(1) for the run.  bl_hook_latency is (0, 0, 0). */
+static int hook_latency(int device, int xor_scheme, int k, int r, int L, int e, long ncalls, int arena, int in_place,
+                        double out[7]) {
     pquic_fec_host_api_t api = {bl_get, bl_set, bl_malloc, bl_free, NULL};
     if (pquic_fec_bind_host(&api, device) || k > 100 || r > 100 || e > r || e > k) return -1;
+    if (xor_scheme && (r != 1 || e != 1)) return -1;
+    if ((arena || in_place) && (!pquic_fec_set_hooks_in_place || !pquic_fec_register_heap)) return -1;
+    const size_t pool_bytes = ((size_t)k * L + 63) & ~(size_t)63;
+    if (arena) {
+        if (arena_map(&g_thread_arena, pool_bytes + (size_t)(4 * (k + r) + 64) * SLOT, 0)) return -1;
+        g_thread_arena.used = pool_bytes;
+        if (pquic_fec_register_heap(g_thread_arena.base, g_thread_arena.bytes)) return -1;
+    }
+    if (in_place && pquic_fec_set_hooks_in_place(1)) return -1;
     picoquic_cnx_t cnx;
     memset(&cnx, 0, sizeof cnx);
-    if (pquic_fec_rlc_create_fec_schemes(&cnx)) return -1;
+    if (xor_scheme ? pquic_fec_xor_create_fec_schemes(&cnx) : pquic_fec_rlc_create_fec_schemes(&cnx)) return -1;
     const protoop_arg_t scheme = cnx.out[0];
-    uint8_t *pool = malloc((size_t)k * L);
+    uint8_t *pool = arena ? g_thread_arena.base : malloc((size_t)k * L);
     pquic_source_symbol_t *ss = calloc((size_t)k, sizeof *ss);
     uint64_t *lat = malloc(sizeof *lat * (size_t)ncalls);
     if (!pool || !ss || !lat) return -1;
@@ -869,7 +889,8 @@ int bl_hook_latency(int device, int k, int r, int L, int e, long ncalls, double 
             cnx.in[1] = scheme;
             /* repairs for this block (untimed when measuring recover) */
             uint64_t t0 = now_us();
-            if (pquic_fec_rlc_generate_repair_symbols(&cnx)) return -1;
+            if (xor_scheme ? pquic_fec_xor_generate_repair_symbols(&cnx) : pquic_fec_rlc_generate_repair_symbols(&cnx))
+                return -1;
             uint64_t t1 = now_us();
             if (op == 1) {
                 fb.current_repair_symbols = (uint8_t)r;
@@ -877,7 +898,7 @@ int bl_hook_latency(int device, int k, int r, int L, int e, long ncalls, double 
                 for (int j = first; j < first + e; j++) fb.source_symbols[j] = NULL;
                 fb.current_source_symbols = (uint8_t)(k - e);
                 t0 = now_us();
-                if (pquic_fec_rlc_recover(&cnx)) return -1;
+                if (xor_scheme ? pquic_fec_xor_recover(&cnx) : pquic_fec_rlc_recover(&cnx)) return -1;
                 t1 = now_us();
                 for (int j = first; j < first + e; j++)
                     if (fb.source_symbols[j]) {
@@ -904,9 +925,34 @@ int bl_hook_latency(int device, int k, int r, int L, int e, long ncalls, double 
         out[3 * op + 2] = sum / ncalls;
     }
     out[6] = (double)recovered / ncalls;
-    bl_free(NULL, (void *)(uintptr_t)scheme);
-    free(pool); free(ss); free(lat);
+    if (scheme) bl_free(NULL, (void *)(uintptr_t)scheme);
+    if (in_place) pquic_fec_set_hooks_in_place(0);
+    if (arena) {
+        pquic_fec_unregister_heap(g_thread_arena.base);
+        arena_unmap(&g_thread_arena);
+    } else {
+        free(pool);
+    }
+    free(ss); free(lat);
     return 0;
+}
+
+int bl_hook_latency(int device, int k, int r, int L, int e, long ncalls, double out[7]) {
+    return hook_latency(device, 0, k, r, L, e, ncalls, 0, 0, out);
+}
+
+/* The same for either scheme, with the symbols on the heap or in a registered arena and the hooks staged or
+ * in place (hook_latency above).  rows[4], if not NULL: the run's movement of pquic_fec_hook_rows_stats --
+ * rows in place, rows staged, calls the worker served, calls launched.  Returns 0, or -1 (also against an
+ * engine library without the in-place mode when arena or in_place is asked for). */
+int bl_hook_latency_mode(int device, int xor_scheme, int k, int r, int L, int e, long ncalls, int arena, int in_place,
+                         double out[7], uint64_t rows[4]) {
+    uint64_t s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+    if (pquic_fec_hook_rows_stats) pquic_fec_hook_rows_stats(s0);
+    const int rc = hook_latency(device, xor_scheme, k, r, L, e, ncalls, arena, in_place, out);
+    if (pquic_fec_hook_rows_stats) pquic_fec_hook_rows_stats(s1);
+    for (int i = 0; rows && i < 4; i++) rows[i] = s1[i] - s0[i];
+    return rc;
 }
 
 /* The synchronous hooks while a bulk job occupies the same GPU: a background thread runs back-to-back
