@@ -370,6 +370,62 @@ int fecgpu_rlc_decode_full(void *src, const void *rep, uint64_t nblocks, uint32_
                            const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
                            uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Span decode (opt-in): the joint decode of the sliding-window framework's overlapping windows.  Every
+ * other decode treats a window as a closed block, so a repair helps only the window it was sent with,
+ * although a source symbol lies in k / step windows.  A span is K consecutive stream symbols (1..128) and
+ * R repair slots (1..128) for the received repairs whose windows lie inside it, with presence masks as
+ * everywhere else.  Repair slot i of span b carries rep_seed[b * R + i] (its FPID, as in
+ * fecgpu_rlc_decode_seeded), rep_off[b * R + i] (the first column its window covers) and
+ * rep_nss[b * R + i] (its window's length): its coefficient row is zero outside [off, off + nss) and the
+ * first nss TinyMT32 coefficients of the seed inside, what the sender used for that window.  A present
+ * repair with nss == 0 or off + nss > K counts as absent.
+ * With n missing columns, m present valid repairs and M their m x n matrix on the missing columns, missing
+ * column u is determined iff e_u lies in the row space of M.  Per span:
+ *   FECGPU_BLOCK_NOTHING    n == 0 or m == 0;
+ *   FECGPU_BLOCK_RECOVERED  at least one column is determined: every determined source is written (the
+ *                           bytes are unique, so they are the original symbol), no other row is.
+ *                           recovered[] has the bit of every determined source whose bytes are not all
+ *                           zero; an all-zero one is written with its bit clear, as in full-rank mode;
+ *   FECGPU_BLOCK_SINGULAR   none is determined: no row is read or written.
+ * FECGPU_BLOCK_REF_UB is never returned, and the reference's received + m >= k precondition does not
+ * apply: fewer repairs than losses can still determine some of them.  Only the lowest-index independent
+ * set of repairs is read (the greedy scan in ascending slot order); a repair that is absent, invalid,
+ * dependent on earlier ones or zero on every missing column is never dereferenced.  Where every repair has
+ * off == 0 and nss == K, and fecgpu_rlc_decode_full with rep_seed recovers the span (or has n == 0 or
+ * m == 0), status, recovered[] and bytes are identical to it.
+ * The workspace is fecgpu_rlc_decode_workspace(nspans, K, R); fecgpu_rlc_span_decode_plan writes the plan
+ * records every decode shares and pairs with fecgpu_rlc_decode_apply, _apply_to and _apply_packed (packed
+ * row u = the u-th determined source, ascending); fecgpu_rlc_span_decode is the plan and the in-place apply
+ * on packed rows src[span][K][L], rep[span][R][L].  Argument errors (K or R out of range, NULL tables,
+ * misalignment, a workspace that is too small) return FECGPU_ERR_INVALID before anything is launched.
+ * Asynchronous on `stream`, nothing allocated. */
+int fecgpu_rlc_span_decode_plan(uint64_t nspans, uint32_t K, uint32_t R, const uint32_t *rep_seed,
+                                const uint8_t *rep_off, const uint8_t *rep_nss, const uint64_t *src_present,
+                                const uint64_t *rep_present, void *workspace, size_t workspace_bytes, void *stream);
+int fecgpu_rlc_span_decode(void *src, const void *rep, uint64_t nspans, uint32_t K, uint32_t R, uint32_t symbol_size,
+                           const uint32_t *rep_seed, const uint8_t *rep_off, const uint8_t *rep_nss,
+                           const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                           uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream);
+/* The span decode on rows by address with a length each: the tables, lengths, clamping and address rules
+ * of fecgpu_rlc_decode_rows_fused_full, plus rep_off and rep_nss.  blk_len[b] is the span's length; a
+ * repair shorter than it counts as zero-padded, which is exact (every source of that window is at most as
+ * long).  Every determined source receives exactly blk_len[b] bytes at its own row; no other row is
+ * written, nothing is written past blk_len[b], and a repair the plan does not select is never
+ * dereferenced. */
+int fecgpu_rlc_span_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                      const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nspans, uint32_t K,
+                                      uint32_t R, uint32_t symbol_size, const uint32_t *rep_seed,
+                                      const uint8_t *rep_off, const uint8_t *rep_nss, const uint64_t *src_present,
+                                      const uint64_t *rep_present, uint8_t *status, uint64_t *recovered,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+/* From a receiver's window to a span (host only, no device): first_id[i] and nss[i] are the window start
+ * (the repair's fec_scheme_specific) and length of received repair i, m of them.  Differences are taken
+ * modulo 2^32 from first_id[0], so ids may wrap.  *base_id is the span's first symbol id, *K its width,
+ * off[i] repair i's first column.  FECGPU_ERR_INVALID when m == 0, a pointer is NULL or the width
+ * exceeds 128. */
+int fecgpu_rlc_span_layout(const uint32_t *first_id, const uint8_t *nss, uint32_t m, uint32_t *base_id, uint32_t *K,
+                           uint8_t *off);
+
 /* XOR decode (r == 1), same conventions. */
 int fecgpu_xor_decode(void *src, const void *rep, uint64_t nblocks, uint32_t k,
                       uint32_t symbol_size, const uint64_t *src_present,
@@ -460,6 +516,15 @@ int fecgpu_rlc_decode_rows_fused_host_full(fecgpu_host_ctx_t *ctx, const uint64_
                                            uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size,
                                            const uint32_t *rep_seed, const uint64_t *src_present,
                                            const uint64_t *rep_present, uint8_t *status, uint64_t *recovered);
+/* fecgpu_rlc_span_decode_rows_fused from the host: host tables, staged like those of the other table forms.
+ * Before any launch it checks blk_len and the lengths as fecgpu_rlc_decode_rows_fused_host does, and
+ * rep_off + rep_nss <= K for every present repair (FECGPU_ERR_INVALID). */
+int fecgpu_rlc_span_decode_rows_fused_host(fecgpu_host_ctx_t *ctx, const uint64_t *src_rows, const uint32_t *src_len,
+                                           const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                           uint64_t nspans, uint32_t K, uint32_t R, uint32_t symbol_size,
+                                           const uint32_t *rep_seed, const uint8_t *rep_off, const uint8_t *rep_nss,
+                                           const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                                           uint64_t *recovered);
 /* fecgpu_rlc_window_encode_table from the host: the stream (host rows) crosses PCIe once, by one copy,
  * before the windows are coded from device memory -- a symbol serves up to k windows, so reading it in
  * place would cross the bus that many times; wrow[] is a host array; repairs go to page-locked `rep` in

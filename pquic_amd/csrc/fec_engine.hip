@@ -917,6 +917,243 @@ __global__ __launch_bounds__(64) void k_rlc_plan_full(uint64_t nblocks, int k, i
 }
 
 // ---------------------------------------------------------------------------------------------
+// Span plan (fecgpu_rlc_span_decode_plan): the joint decode of the sliding-window framework's
+// overlapping windows.  A span is k consecutive stream symbols and the received repairs whose windows
+// lie inside it; repair i covers columns [off_i, off_i + nss_i) with the first nss_i TinyMT32
+// coefficients of its seed and is zero elsewhere.  One wave runs plan_full_wave_block's scan -- the
+// basis [A | V] of the accepted repairs in reduced row echelon form, the received repairs offered in
+// ascending order -- with these differences: the rows are banded, the scan runs until the repairs are
+// exhausted or the rank equals n (fewer repairs than unknowns can still determine some of them), and
+// the determined unknowns are read off the basis: unknown pc[t] is determined iff basis row t is zero
+// on every other missing column (e_u lies in the row space).  Only their rows go into the record, so
+// the data pass writes exactly the determined sources.  The determined set is kept up to date after
+// every accepted repair: a repair whose window's missing columns are all determined is dependent and
+// is skipped by a mask test, and one whose window holds no missing column is not offered at all.
+// The accepted repair number t stands in for the input of missing column unk[t] (as in the full-rank
+// plan); a missing column past the rank has no repair, carries coefficient 0 in every row and names
+// the first selected repair, a row the data pass reads anyway.
+// LDS: log/exp | R[r][kpad] banded rows of the received repairs | B[em][pad16(2k)] basis rows (rank
+//      <= min(m, n) <= em rows, n + k <= 2k <= 256 columns: A columns 0..n-1, then V)
+//      | unk, cand, sel, pc, rowof int[128] | fac[128] | 16:
+//      768 + r * pad16(k) + min(k, r) * pad16(2 k) + 2560 + 128 + 16 bytes, 52 624 at k = r = 128.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ constexpr static inline size_t plan_span_lds_bytes(uint32_t k, uint32_t r) {
+  const uint32_t em = k < r ? k : r;
+  return 768 + (size_t)r * pad16(k) + (size_t)em * pad16(2 * k) + 4 * (128 * 5) + 128 + 16;
+}
+
+// Columns o .. e - 1 of a span as a 128-bit mask (0 <= o < e <= 128).
+__device__ __forceinline__ void win128(int o, int e, uint64_t &w0, uint64_t &w1) {
+  const uint64_t a0 = o < 64 ? ~0ull << o : 0ull, a1 = o < 64 ? ~0ull : ~0ull << (o - 64);
+  const uint64_t b0 = e < 64 ? (1ull << e) - 1 : ~0ull;
+  const uint64_t b1 = e <= 64 ? 0ull : e < 128 ? (1ull << (e - 64)) - 1 : ~0ull;
+  w0 = a0 & b0;
+  w1 = a1 & b1;
+}
+
+// One span's plan by one wave of a one-wave workgroup.  `lds` holds the log/exp tables at 0 and room
+// for plan_span_lds_bytes(k, r).  Every lane must call it; control flow is wave-uniform.
+__device__ __forceinline__ void plan_span_wave_block(uint64_t b, int k, int r, const uint32_t *seeds,
+                                                     const uint8_t *roff, const uint8_t *rnss, const uint64_t *sp,
+                                                     const uint64_t *rp, uint8_t *ws, uint8_t *lds) {
+  const WsLayout L = ws_layout((uint32_t)k, (uint32_t)r);
+  const int lane = threadIdx.x;
+  const int em = (int)L.em;
+  const int kpad = (int)pad16((uint32_t)k);
+  uint8_t *EXP = lds, *LOG = lds + 512;
+  uint8_t *R = lds + 768;
+  uint8_t *B = R + (size_t)r * kpad;
+  int *unk = reinterpret_cast<int *>(B + (size_t)em * pad16((uint32_t)(2 * k)));
+  int *cand = unk + 128, *sel = unk + 256, *pc = unk + 384, *rowof = unk + 512;
+  uint8_t *fac = reinterpret_cast<uint8_t *>(unk + 640);
+  uint8_t *h = ws + b * (uint64_t)L.stride;
+
+  uint64_t s0 = sp[2 * b], s1 = sp[2 * b + 1], q0 = rp[2 * b], q1 = rp[2 * b + 1];
+  clip128(s0, s1, k);
+  clip128(q0, q1, r);
+  uint64_t m0 = ~s0, m1 = ~s1;  // the missing columns
+  clip128(m0, m1, k);
+  // A present repair whose window is empty or leaves the span counts as absent (valid).  One whose window
+  // holds no missing column is zero on them all: the scan would reject it, so it is not offered (live).
+  int valid = 0;
+  {
+    const uint64_t rb = b * (uint64_t)r;
+    bool ok[2] = {false, false}, live[2] = {false, false};
+#pragma unroll
+    for (int x = 0; x < 2; x++) {
+      const int i = lane + 64 * x;
+      if (i < r && (((x ? q1 : q0) >> lane) & 1)) {
+        const int o = roff[rb + i], w = rnss[rb + i], e = o + w;
+        ok[x] = w >= 1 && e <= k;
+        if (ok[x]) {
+          uint64_t w0, w1;
+          win128(o, e, w0, w1);
+          live[x] = ((w0 & m0) | (w1 & m1)) != 0;
+        }
+      }
+    }
+    valid = __popcll(__ballot(ok[0])) + __popcll(__ballot(ok[1]));
+    q0 = __ballot(live[0]);
+    q1 = __ballot(live[1]);
+  }
+  const int n = k - (__popcll(s0) + __popcll(s1));  // unknowns
+  const int m = __popcll(q0) + __popcll(q1);        // equations offered
+  __syncthreads();  // the previous span's LDS reads are done
+  if (n == 0 || valid == 0) {
+    if (lane == 0) { h[0] = FECGPU_BLOCK_NOTHING; h[1] = 0; }
+    return;
+  }
+  if (m == 0) {  // repairs were received, none of them covers a missing source
+    if (lane == 0) { h[0] = FECGPU_BLOCK_SINGULAR; h[1] = 0; }
+    return;
+  }
+  const int wpad = (int)pad16((uint32_t)(n + k));
+  for (int j = lane; j < k; j += 64)
+    if (bit128(m0, m1, j)) unk[rank128(m0, m1, j)] = j;
+  for (int i = lane; i < r; i += 64)  // candidate: slot | first column << 8 | length << 16
+    if (bit128(q0, q1, i))
+      cand[rank128(q0, q1, i)] = i | roff[b * (uint64_t)r + i] << 8 | rnss[b * (uint64_t)r + i] << 16;
+  for (int x = lane; x < m * (kpad >> 2); x += 64) reinterpret_cast<uint32_t *>(R)[x] = 0u;  // zero outside the windows
+  __syncthreads();
+  for (int e = lane; e < m; e += 64) {  // banded TinyMT32 row of every repair offered
+    const int o = (cand[e] >> 8) & 0xff, w = cand[e] >> 16;
+    Tmt t;
+    tmt_init(t, seeds[b * (uint64_t)r + (uint32_t)(cand[e] & 0xff)]);
+    uint8_t *row = R + e * kpad + o;
+    for (int j = 0; j < w; j++) row[j] = tmt_coef(t);
+  }
+  __syncthreads();
+  const int w = n + k;
+  const int nq = (w + 63) >> 6;  // column registers in use
+  int cnt = 0;
+  uint64_t d0 = 0, d1 = 0;    // determined unknowns so far, by unknown number
+  uint64_t dc0 = 0, dc1 = 0;  // the same by column
+  for (int e = 0; e < m && cnt < n; e++) {  // until the repairs are exhausted or the rank is n
+    {  // a repair whose window's missing columns are all determined already lies in the basis' span: dependent,
+       // skipped without the elimination (a span of many windows offers mostly such repairs)
+      uint64_t w0, w1;
+      const int o = (cand[e] >> 8) & 0xff;
+      win128(o, o + (cand[e] >> 16), w0, w1);
+      if (((w0 & m0 & ~dc0) | (w1 & m1 & ~dc1)) == 0) continue;
+    }
+    const uint8_t *row = R + e * kpad;
+    // the candidate's factor against basis row t is its entry at pivot column pc[t] (log, 255 = zero)
+    for (int t = lane; t < cnt; t += 64) {
+      const uint32_t a = row[unk[pc[t]]];
+      fac[t] = a ? LOG[a] : (uint8_t)255;
+    }
+    __syncthreads();
+    // candidate row as it would stand at position cnt (plan_full_wave_block): A[u] = row[unk[u]];
+    // V[j] = row[j] for a present source and 1 at the slot unk[cnt] it would take, minus the basis
+    uint32_t wv[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      if (q >= nq) continue;  // wave-uniform
+      const int c = lane + 64 * q;
+      const int cc = c < w ? c : w - 1;
+      uint32_t v;
+      if (cc < n) v = row[unk[cc]];
+      else {
+        const int j = cc - n;
+        v = bit128(m0, m1, j) ? (uint32_t)(unk[cnt] == j) : (uint32_t)row[j];
+      }
+#pragma unroll 4
+      for (int t = 0; t < cnt; t++) {
+        const uint32_t ft = fac[t];
+        const uint32_t bv = B[t * wpad + cc];
+        const uint32_t pr = EXP[ft + LOG[bv]];
+        v ^= (bv != 0 && ft != 255u) ? pr : 0u;
+      }
+      wv[q] = c < w ? v : 0u;
+    }
+    // pivot: the first missing column where the reduced candidate is non-zero (A columns: c < n <= 128)
+    const uint64_t z0 = __ballot(lane < n && wv[0] != 0);
+    const uint64_t z1 = __ballot(lane + 64 < n && wv[1] != 0);
+    __syncthreads();  // fac[] has been read by every lane
+    if ((z0 | z1) == 0) continue;  // dependent, or zero on every missing column: never read by the data pass
+    const int p = z0 ? __ffsll((unsigned long long)z0) - 1 : 64 + __ffsll((unsigned long long)z1) - 1;
+    const uint32_t pv = p < 64 ? (uint32_t)__shfl((int)wv[0], p, 64) : (uint32_t)__shfl((int)wv[1], p - 64, 64);
+    const uint32_t li = 255u - LOG[pv];  // log of 1 / pivot
+#pragma unroll
+    for (int q = 0; q < 4; q++) {  // normalised row into the basis
+      const int c = lane + 64 * q;
+      wv[q] = wv[q] ? (uint32_t)EXP[LOG[wv[q]] + li] : 0u;
+      if (c < w) B[cnt * wpad + c] = (uint8_t)wv[q];
+    }
+    if (lane == 0) { pc[cnt] = p; sel[cnt] = cand[e] & 0xff; }
+    for (int t = lane; t < cnt; t += 64) {  // clear column p of the earlier basis rows
+      const uint32_t a = B[t * wpad + p];
+      fac[t] = a ? LOG[a] : (uint8_t)255;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      if (q >= nq) continue;  // wave-uniform
+      const int c = lane + 64 * q;
+      const int cc = c < w ? c : w - 1;
+      const bool live = c < w && wv[q] != 0;
+      const uint32_t lw = LOG[wv[q]];
+      for (int t = 0; t < cnt; t++) {
+        const uint32_t ft = fac[t];
+        if (live && ft != 255u) B[t * wpad + cc] ^= EXP[ft + lw];
+      }
+    }
+    cnt++;
+    __syncthreads();
+    // the determined unknowns: basis rows that are zero on every missing column but their pivot's
+    d0 = d1 = 0;
+    for (int t = 0; t < cnt; t++) {
+      const int pt = pc[t];
+      const bool x0 = lane < n && lane != pt && B[t * wpad + lane] != 0;
+      const bool x1 = lane + 64 < n && lane + 64 != pt && B[t * wpad + (lane + 64 < n ? lane + 64 : 0)] != 0;
+      if ((__ballot(x0) | __ballot(x1)) != 0) continue;
+      if (pt < 64) d0 |= 1ull << pt; else d1 |= 1ull << (pt - 64);
+      if (lane == 0) rowof[pt] = t;
+    }
+    dc0 = __ballot(lane < k && bit128(m0, m1, lane) && bit128(d0, d1, rank128(m0, m1, lane)));
+    dc1 = __ballot(lane + 64 < k && bit128(m0, m1, lane + 64) && bit128(d0, d1, rank128(m0, m1, lane + 64)));
+  }
+  const int ne = __popcll(d0) + __popcll(d1);
+  if (ne == 0) {  // the received repairs determine no missing source
+    if (lane == 0) { h[0] = FECGPU_BLOCK_SINGULAR; h[1] = 0; }
+    return;
+  }
+  for (int u = lane; u < n; u += 64)
+    if (bit128(d0, d1, u)) {
+      const int i = rank128(d0, d1, u);  // determined unknowns in ascending source order
+      cand[i] = u;
+      h[L.off_unk + i] = (uint8_t)unk[u];
+      h[L.off_nz + i] = 0;
+    }
+  for (int t = lane; t < cnt; t += 64) h[L.off_sel + t] = (uint8_t)sel[t];
+  __syncthreads();
+  for (int x = lane; x < ne * ne; x += 64) {  // a determined unknown depends on no other
+    const int i = x / ne, u = x - i * ne;
+    h[L.off_dep + i * em + u] = 0;
+  }
+  for (int x = lane; x < ne * k; x += 64) {
+    const int i = x / k, j = x - i * k;
+    h[L.off_D + i * k + j] = B[rowof[cand[i]] * wpad + n + j];
+  }
+  // slot map: input j = source j if present, else the repair accepted for its unknown; past the rank the
+  // first selected repair (coefficient 0 in every row, a row the pass reads anyway)
+  for (int j = lane; j < k; j += 64) {
+    const int u = rank128(m0, m1, j);
+    h[L.off_slot + j] = bit128(m0, m1, j) ? (uint8_t)(0x80 | sel[u < cnt ? u : 0]) : (uint8_t)j;
+  }
+  if (lane == 0) { h[0] = FECGPU_BLOCK_RECOVERED; h[1] = (uint8_t)ne; }
+}
+
+__global__ __launch_bounds__(64) void k_rlc_plan_span(uint64_t nspans, int k, int r, const uint32_t *seeds,
+                                                      const uint8_t *roff, const uint8_t *rnss, const uint64_t *sp,
+                                                      const uint64_t *rp, uint8_t *ws) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  plan_load_tables(lds);
+  for (uint64_t b = blockIdx.x; b < nspans; b += gridDim.x)
+    plan_span_wave_block(b, k, r, seeds, roff, rnss, sp, rp, ws, lds);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Lane-per-block plan (small systems): one lane replays fec_recover's coefficient work for one
 // block.  GF(2^8) products through log/exp tables in LDS; each lane's working set (A: em x em,
 // V: em x k, lists) lives in LDS byte-interleaved across the wave (element e of lane l at
@@ -4327,6 +4564,46 @@ int fecgpu_rlc_decode_plan_full(uint64_t nblocks, uint32_t k, uint32_t r, uint32
                                src_present, rep_present, workspace, workspace_bytes, stream);
 }
 
+// The span plan's arguments, checked before anything is launched (the span entry points share it).
+static int span_plan_args(uint64_t nspans, uint32_t k, uint32_t r, const uint32_t *rep_seed, const uint8_t *rep_off,
+                          const uint8_t *rep_nss, const uint64_t *src_present, const uint64_t *rep_present,
+                          const void *workspace, size_t workspace_bytes) {
+  if (k < 1 || k > FECGPU_MAX_K) return set_err(FECGPU_ERR_INVALID, "%s", "span: K out of range [1,128]");
+  if (r < 1 || r > FECGPU_MAX_R) return set_err(FECGPU_ERR_INVALID, "%s", "span: R out of range [1,128]");
+  if (nspans == 0) return FECGPU_OK;
+  if (!rep_seed || !rep_off || !rep_nss) return set_err(FECGPU_ERR_INVALID, "%s", "span: NULL rep_seed / rep_off / rep_nss");
+  if (!src_present || !rep_present) return set_err(FECGPU_ERR_INVALID, "%s", "span: NULL presence mask");
+  if (!workspace) return set_err(FECGPU_ERR_INVALID, "%s", "span: NULL workspace");
+  if ((uintptr_t)rep_seed % 4) return set_err(FECGPU_ERR_INVALID, "%s", "span: rep_seed must be 4-byte aligned");
+  if ((uintptr_t)src_present % 8 || (uintptr_t)rep_present % 8)
+    return set_err(FECGPU_ERR_INVALID, "%s", "span: presence masks must be 8-byte aligned");
+  if ((uintptr_t)workspace % 16) return set_err(FECGPU_ERR_INVALID, "%s", "span: workspace must be 16-byte aligned");
+  if (workspace_bytes < fecgpu_rlc_decode_workspace(nspans, k, r))
+    return set_err(FECGPU_ERR_INVALID, "%s", "span: workspace smaller than fecgpu_rlc_decode_workspace(nspans, K, R)");
+  return FECGPU_OK;
+}
+
+static int span_plan_launch(uint64_t nspans, uint32_t k, uint32_t r, const uint32_t *rep_seed, const uint8_t *rep_off,
+                            const uint8_t *rep_nss, const uint64_t *src_present, const uint64_t *rep_present,
+                            void *workspace, hipStream_t s) {
+  // 52 624 B at K = R = 128, the largest shape: the default dynamic-LDS limit holds for every shape
+  static_assert(plan_span_lds_bytes(FECGPU_MAX_K, FECGPU_MAX_R) <= 65536, "span plan LDS within the default limit");
+  hipLaunchKernelGGL(k_rlc_plan_span, dim3(grid_for(nspans)), dim3(64), plan_span_lds_bytes(k, r), s, nspans, (int)k,
+                     (int)r, rep_seed, rep_off, rep_nss, src_present, rep_present, (uint8_t *)workspace);
+  HIPCHK(hipGetLastError());
+  return FECGPU_OK;
+}
+
+int fecgpu_rlc_span_decode_plan(uint64_t nspans, uint32_t k, uint32_t r, const uint32_t *rep_seed,
+                                const uint8_t *rep_off, const uint8_t *rep_nss, const uint64_t *src_present,
+                                const uint64_t *rep_present, void *workspace, size_t workspace_bytes, void *stream) {
+  int rc = span_plan_args(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace,
+                          workspace_bytes);
+  if (rc || nspans == 0) return rc;
+  return span_plan_launch(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace,
+                          (hipStream_t)stream);
+}
+
 static int launch_finalize(uint64_t nblocks, uint32_t k, uint32_t r, uint8_t *status, uint64_t *recovered,
                            const uint8_t *ws, hipStream_t s) {
   const uint32_t fgrid = (uint32_t)((nblocks + 255) / 256 < 65536 ? (nblocks + 255) / 256 : 65536);
@@ -4688,6 +4965,26 @@ int fecgpu_rlc_encode_rows_fused(const uint64_t *src_rows, const uint32_t *src_l
   return FECGPU_OK;
 }
 
+// The data pass of the fused row forms over the plan records in ws (any plan: reference, full-rank, span).
+static int decode_rows_fused_pass(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                  const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
+                                  uint32_t r, uint32_t symbol_size, uint8_t *status, uint64_t *recovered, uint8_t *ws,
+                                  hipStream_t s) {
+  count_decode(nblocks);
+  const WsLayout WL = ws_layout(k, r);
+  if (r == 0) return launch_finalize(nblocks, k, r, status, recovered, ws, s);
+  if (int rc2 = bs_table_check()) return rc2;
+  const int rt = decode_tile(WL.em);
+  const BsCfg cfg = pick_bs_cfg((int)symbol_size);
+  const bool fused = (int)WL.em <= rt;
+  for (int r0 = 0; r0 < (int)WL.em; r0 += rt) {
+    FEC_BS_DISPATCH(launch_recover_rows_fused, src_rows, rep_rows, src_len, rep_len, blk_len, nblocks, (int)k, (int)r,
+                    (int)symbol_size, cfg, ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s)
+  }
+  HIPCHK(hipGetLastError());
+  return fused ? FECGPU_OK : launch_finalize(nblocks, k, r, status, recovered, ws, s);
+}
+
 extern "C" __attribute__((visibility("hidden"))) int fecgpu_rlc_decode_rows_fused_internal(
     const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows, const uint32_t *rep_len,
     const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
@@ -4702,20 +4999,8 @@ extern "C" __attribute__((visibility("hidden"))) int fecgpu_rlc_decode_rows_fuse
   if ((rc = (full ? decode_plan_full_impl : decode_plan_impl)(nblocks, k, r, 0, nullptr, rep_seed, src_present,
                                                               rep_present, workspace, workspace_bytes, s)))
     return rc;
-  count_decode(nblocks);
-  uint8_t *ws = (uint8_t *)workspace;
-  const WsLayout WL = ws_layout(k, r);
-  if (r == 0) return launch_finalize(nblocks, k, r, status, recovered, ws, s);
-  if (int rc2 = bs_table_check()) return rc2;
-  const int rt = decode_tile(WL.em);
-  const BsCfg cfg = pick_bs_cfg((int)symbol_size);
-  const bool fused = (int)WL.em <= rt;
-  for (int r0 = 0; r0 < (int)WL.em; r0 += rt) {
-    FEC_BS_DISPATCH(launch_recover_rows_fused, src_rows, rep_rows, src_len, rep_len, blk_len, nblocks, (int)k, (int)r,
-                    (int)symbol_size, cfg, ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s)
-  }
-  HIPCHK(hipGetLastError());
-  return fused ? FECGPU_OK : launch_finalize(nblocks, k, r, status, recovered, ws, s);
+  return decode_rows_fused_pass(src_rows, src_len, rep_rows, rep_len, blk_len, nblocks, k, r, symbol_size, status,
+                                recovered, (uint8_t *)workspace, s);
 }
 
 int fecgpu_rlc_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
@@ -4844,6 +5129,48 @@ int fecgpu_rlc_decode_full(void *src, const void *rep, uint64_t nblocks, uint32_
   return decode_impl(src, rep, src, nblocks, k, r, symbol_size, rep_seed ? 0 : fbn_base, rep_seed ? nullptr : fbn,
                      rep_seed, src_present, rep_present, status, recovered, workspace, workspace_bytes,
                      (hipStream_t)stream, 1);
+}
+
+// Span decode: the span plan, then the data pass every decode shares, in place on the packed rows.
+int fecgpu_rlc_span_decode(void *src, const void *rep, uint64_t nspans, uint32_t k, uint32_t r, uint32_t symbol_size,
+                           const uint32_t *rep_seed, const uint8_t *rep_off, const uint8_t *rep_nss,
+                           const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status,
+                           uint64_t *recovered, void *workspace, size_t workspace_bytes, void *stream) {
+  int rc = span_plan_args(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace,
+                          workspace_bytes);
+  if (rc || nspans == 0) return rc;
+  if ((rc = check_common(src, rep, nspans, k, r, symbol_size))) return rc;
+  if (!status || !recovered) return set_err(FECGPU_ERR_INVALID, "%s", "span: NULL status / recovered");
+  if ((uintptr_t)recovered % 8) return set_err(FECGPU_ERR_INVALID, "%s", "span: recovered must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = span_plan_launch(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace, s)))
+    return rc;
+  return decode_apply_impl(src, rep, src, nspans, k, r, symbol_size, status, recovered, workspace, workspace_bytes, s);
+}
+
+// The same with rows by address and a length each: the span plan, then the fused row forms' data pass.
+int fecgpu_rlc_span_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
+                                      const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nspans, uint32_t k,
+                                      uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
+                                      const uint8_t *rep_off, const uint8_t *rep_nss, const uint64_t *src_present,
+                                      const uint64_t *rep_present, uint8_t *status, uint64_t *recovered,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
+  int rc = span_plan_args(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace,
+                          workspace_bytes);
+  if (rc || nspans == 0) return rc;
+  if ((rc = check_common(src_rows, rep_rows, nspans, k, r, symbol_size))) return rc;
+  if (((uintptr_t)src_rows | (uintptr_t)rep_rows) % 8)
+    return set_err(FECGPU_ERR_INVALID, "%s", "span: row tables must be 8-byte aligned");
+  if (!src_len || !rep_len || !blk_len) return set_err(FECGPU_ERR_INVALID, "%s", "span: NULL length table");
+  if (((uintptr_t)src_len | (uintptr_t)rep_len | (uintptr_t)blk_len) % 4)
+    return set_err(FECGPU_ERR_INVALID, "%s", "span: length tables must be 4-byte aligned");
+  if (!status || !recovered) return set_err(FECGPU_ERR_INVALID, "%s", "span: NULL status / recovered");
+  if ((uintptr_t)recovered % 8) return set_err(FECGPU_ERR_INVALID, "%s", "span: recovered must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = span_plan_launch(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace, s)))
+    return rc;
+  return decode_rows_fused_pass(src_rows, src_len, rep_rows, rep_len, blk_len, nspans, k, r, symbol_size, status,
+                                recovered, (uint8_t *)workspace, s);
 }
 
 // host_path.hip: decode with the recovered rows to dst (library-internal); full != 0: full-rank mode

@@ -854,6 +854,46 @@ int fecgpu_rlc_decode_rows_fused_host_full(fecgpu_host_ctx_t *c, const uint64_t 
                                 status, recovered, 1);
 }
 
+// The span decode on rows (fecgpu_rlc_span_decode_rows_fused): the fused decode's tables and the two u8
+// tables of the repairs' windows, through the same stager and slice loop.
+int fecgpu_rlc_span_decode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,
+                                           const uint64_t *rep_rows, const uint32_t *rep_len, const uint32_t *blk_len,
+                                           uint64_t nblocks, uint32_t k, uint32_t r, uint32_t L, const uint32_t *seeds,
+                                           const uint8_t *rep_off, const uint8_t *rep_nss, const uint64_t *sp,
+                                           const uint64_t *rp, uint8_t *status, uint64_t *recovered) {
+  if (!src_rows || !src_len || !blk_len || !rep_rows || !rep_len || !seeds || !rep_off || !rep_nss)
+    return rows_len_invalid("NULL row / length / window table");
+  if (!sp || !rp || !status || !recovered) return rows_len_invalid("NULL mask/status");
+  if (int rc = rows_len_shape(k, r, L)) return rc;
+  if (r < 1) return rows_len_invalid("span: R out of range [1,128]");
+  if (int rc = rows_len_check(src_len, blk_len, sp, nblocks, k, L)) return rc;
+  for (uint64_t b = 0; b < nblocks; b++)
+    for (uint32_t i = 0; i < r; i++)
+      if (((rp[2 * b + (i >> 6)] >> (i & 63)) & 1) && (uint32_t)rep_off[b * r + i] + rep_nss[b * r + i] > k)
+        return rows_len_invalid("span: rep_off + rep_nss above K");
+  if (!c) return rows_len_invalid("NULL host context");
+  if (!nblocks) return FECGPU_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  HCHK(hipSetDevice(c->device));
+  enum { SRC, SLEN, BLEN, REP, RLEN, SEED, OFF, NSS, SP, RP, ST, REC };
+  Table t[] = {in(src_rows, k * 8), in(src_len, k * 4), in(blk_len, 4), in(rep_rows, r * 8), in(rep_len, r * 4),
+               in(seeds, r * 4),    in(rep_off, r),     in(rep_nss, r), in(sp, 16),        in(rp, 16),
+               out(status, 1),      out(recovered, 16)};
+  bool in_place;
+  int rc = stage_tables(c, t, nblocks, &in_place);
+  const size_t bb = (size_t)(k + r) * L;
+  if (!rc)
+    rc = for_slices(c, nblocks, bb, sub_batch(c, nblocks, bb), in_place, [&](uint64_t b0, uint64_t m, Slot &w) {
+      HCHK(grow(&w.d_ws, &w.cap_ws, fecgpu_rlc_decode_workspace(m, k, r)));
+      return fecgpu_rlc_span_decode_rows_fused(
+          t[SRC].at<const uint64_t>(b0), t[SLEN].at<const uint32_t>(b0), t[REP].at<const uint64_t>(b0),
+          t[RLEN].at<const uint32_t>(b0), t[BLEN].at<const uint32_t>(b0), m, k, r, L, t[SEED].at<const uint32_t>(b0),
+          t[OFF].at<const uint8_t>(b0), t[NSS].at<const uint8_t>(b0), t[SP].at<const uint64_t>(b0),
+          t[RP].at<const uint64_t>(b0), t[ST].at<uint8_t>(b0), t[REC].at<uint64_t>(b0), w.d_ws, w.cap_ws, w.st);
+    });
+  return finish(c, unstage_tables(c, t, nblocks, in_place, rc));
+}
+
 // ---- XOR on rows (fecgpu_xor_encode_rows_host / fecgpu_xor_decode_rows_host) ----
 // One pass and no packed arrays: a sub-batch needs nothing of its slot but the stream.
 int fecgpu_xor_encode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *src_rows, const uint32_t *src_len,

@@ -135,6 +135,14 @@ def load_library(path: str = LIB_PATH, private: bool = False):
         L.fecgpu_block_svc_rlc_decode_rows.argtypes = [v, v, v, v, v, u32, u32, u32, v, v, v, C.c_int, v, v]
         L.fecgpu_block_svc_xor_encode_rows.argtypes = [v, v, v, u64, u32, u32]
         L.fecgpu_block_svc_xor_decode_rows.argtypes = [v, v, v, u64, u32, u32, v, v, v, v]
+    if hasattr(L, "fecgpu_rlc_span_decode") or not private:  # a private (A/B) load may be an older build
+        L.fecgpu_rlc_span_decode_plan.argtypes = [u64, u32, u32, v, v, v, v, v, v, sz, v]
+        L.fecgpu_rlc_span_decode.argtypes = [v, v, u64, u32, u32, u32, v, v, v, v, v, v, v, v, sz, v]
+        L.fecgpu_rlc_span_decode_rows_fused.argtypes = [v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v, v, v, v,
+                                                        sz, v]
+        L.fecgpu_rlc_span_decode_rows_fused_host.argtypes = [v, v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v, v,
+                                                             v]
+        L.fecgpu_rlc_span_layout.argtypes = [v, v, u32, C.POINTER(u32), C.POINTER(u32), v]
     if hasattr(L, "fecgpu_rlc_window_encode_table"):
         L.fecgpu_rlc_window_encode_table.argtypes = [v, u64, v, u64, u32, u32, u32, v, v]
     if not private:
@@ -150,6 +158,25 @@ def _addr(x):
     if hasattr(x, "data_ptr"):
         return x.data_ptr()
     return x.ctypes.data  # numpy (host-resident path)
+
+
+def span_layout(first_id, nss):
+    """fecgpu_rlc_span_layout (host only): the received repairs' window starts and lengths -> (base_id, K,
+    off), the span's first symbol id, its width and every repair's first column (numpy u8).  Ids may wrap
+    modulo 2^32; raises FecGpuError when there is no repair or the windows span more than 128 symbols."""
+    import numpy as np
+    L = load_library()
+    ids = np.ascontiguousarray(first_id, dtype=np.uint32)
+    n = np.ascontiguousarray(nss, dtype=np.uint8)
+    if ids.shape != n.shape or ids.ndim != 1:
+        raise ValueError("span_layout: first_id and nss must be one-dimensional and of one length")
+    off = np.zeros(max(len(ids), 1), np.uint8)
+    base, K = C.c_uint32(0), C.c_uint32(0)
+    rc = L.fecgpu_rlc_span_layout(ids.ctypes.data, n.ctypes.data, len(ids), C.byref(base), C.byref(K),
+                                  off.ctypes.data)
+    if rc != OK:
+        raise FecGpuError(f"fecgpu_rlc_span_layout failed ({rc}): {L.fecgpu_last_error().decode()}")
+    return base.value, K.value, off[:len(ids)]
 
 
 class Engine:
@@ -314,6 +341,42 @@ class Engine:
                                                          _addr(src_present), _addr(rep_present), _addr(workspace),
                                                          workspace.numel(), self._stream(stream)),
                     "fecgpu_rlc_decode_plan_full")
+
+    def rlc_span_decode_plan(self, rep_seed, rep_off, rep_nss, src_present, rep_present, K, R, nspans, workspace,
+                             stream=None):
+        """fecgpu_rlc_span_decode_plan: the span decode's plan (rep_off / rep_nss: u8 device arrays
+        [nspans][R]); pairs with rlc_decode_apply, _apply_to and _apply_packed."""
+        self._check(self.lib.fecgpu_rlc_span_decode_plan(nspans, K, R, _addr(rep_seed), _addr(rep_off),
+                                                         _addr(rep_nss), _addr(src_present), _addr(rep_present),
+                                                         _addr(workspace), workspace.numel(), self._stream(stream)),
+                    "fecgpu_rlc_span_decode_plan")
+
+    def rlc_span_decode(self, src, rep, rep_seed, rep_off, rep_nss, src_present, rep_present, status, recovered,
+                        K: int, R: int, L: int, nspans: int | None = None, workspace=None, stream=None):
+        """fecgpu_rlc_span_decode: the joint decode of overlapping windows -- every missing source the received
+        repairs of the span determine is recovered in place, also when the whole span is not determined."""
+        nb = nspans if nspans is not None else src.numel() // (K * L)
+        if workspace is None:
+            workspace = self.alloc_workspace(nb, K, R)
+        self._check(self.lib.fecgpu_rlc_span_decode(
+            _addr(src), _addr(rep), nb, K, R, L, _addr(rep_seed), _addr(rep_off), _addr(rep_nss),
+            _addr(src_present), _addr(rep_present), _addr(status), _addr(recovered), _addr(workspace),
+            workspace.numel(), self._stream(stream)), "fecgpu_rlc_span_decode")
+        return status, recovered
+
+    def rlc_span_decode_rows_fused(self, src_rows, src_len, rep_rows, rep_len, blk_len, rep_seed, rep_off, rep_nss,
+                                   src_present, rep_present, status, recovered, nspans: int, K: int, R: int, L: int,
+                                   workspace=None, stream=None):
+        """fecgpu_rlc_span_decode_rows_fused: the span decode on rows by address with a length each; every
+        determined source receives exactly blk_len[b] bytes."""
+        if workspace is None:
+            workspace = self.alloc_workspace(nspans, K, R)
+        self._check(self.lib.fecgpu_rlc_span_decode_rows_fused(
+            _addr(src_rows), _addr(src_len), _addr(rep_rows), _addr(rep_len), _addr(blk_len), nspans, K, R, L,
+            _addr(rep_seed), _addr(rep_off), _addr(rep_nss), _addr(src_present), _addr(rep_present),
+            _addr(status), _addr(recovered), _addr(workspace), workspace.numel(), self._stream(stream)),
+            "fecgpu_rlc_span_decode_rows_fused")
+        return status, recovered
 
     def rlc_decode_stages(self, src, rep, src_present, rep_present, status, recovered, k, r, L, nblocks,
                           workspace, fbn_base=0, stream=None, events=None, dst=None, packed=False):
@@ -598,6 +661,15 @@ class HostPath:
                                                                   nblocks, k, r, L, _addr(seeds), _addr(sp),
                                                                   _addr(rp), _addr(status), _addr(rec)),
                   "fecgpu_rlc_decode_rows_fused_host_full")
+
+    def rlc_span_decode_rows_fused(self, src_rows, src_len, rep_rows, rep_len, blk_len, seeds, rep_off, rep_nss, sp,
+                                   rp, status, rec, nspans, K, R, L):
+        """fecgpu_rlc_span_decode_rows_fused_host: host tables, lengths, seeds, windows, masks, status and
+        recovered; the rows must be device-accessible."""
+        self._chk(self.lib.fecgpu_rlc_span_decode_rows_fused_host(
+            self.ctx, _addr(src_rows), _addr(src_len), _addr(rep_rows), _addr(rep_len), _addr(blk_len), nspans, K,
+            R, L, _addr(seeds), _addr(rep_off), _addr(rep_nss), _addr(sp), _addr(rp), _addr(status), _addr(rec)),
+            "fecgpu_rlc_span_decode_rows_fused_host")
 
     def xor_encode_rows(self, src_rows, src_len, rep_rows, blk_len, nblocks, k, L):
         """fecgpu_xor_encode_rows_host: host tables and lengths; the rows must be device-accessible."""
