@@ -398,7 +398,13 @@ int fecgpu_rlc_decode_full(void *src, const void *rep, uint64_t nblocks, uint32_
  * row u = the u-th determined source, ascending); fecgpu_rlc_span_decode is the plan and the in-place apply
  * on packed rows src[span][K][L], rep[span][R][L].  Argument errors (K or R out of range, NULL tables,
  * misalignment, a workspace that is too small) return FECGPU_ERR_INVALID before anything is launched.
- * Asynchronous on `stream`, nothing allocated. */
+ * Asynchronous on `stream`, nothing allocated.
+ * Knob "span_compact" (fecgpu_set_knob; 0/1, default 1): the data pass of a span decode -- these entry
+ * points, the row forms below, and an apply call on the workspace the last fecgpu_rlc_span_decode_plan call
+ * filled -- lists per tile of unknowns only the input rows with a non-zero coefficient for one of them, so a
+ * row no unknown of the tile depends on is not read; 0 streams all K columns as before.  Same bytes either
+ * way.  The LDS-ring tiles (16 unknowns on packed rows, knob "ring") keep all K; the reference-faithful and
+ * full-rank decodes never compact. */
 int fecgpu_rlc_span_decode_plan(uint64_t nspans, uint32_t K, uint32_t R, const uint32_t *rep_seed,
                                 const uint8_t *rep_off, const uint8_t *rep_nss, const uint64_t *src_present,
                                 const uint64_t *rep_present, void *workspace, size_t workspace_bytes, void *stream);

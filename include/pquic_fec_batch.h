@@ -64,6 +64,8 @@ typedef struct {
     uint64_t job_alloc_us;          /* caller-thread time in those allocations */
     uint64_t deadline_holds;        /* polls that kept an overdue queue open: no idle job for its successor while
                                      * two or more were in flight (flushed at the first poll with one back) */
+    uint64_t spans, span_symbols;   /* spans decoded by span jobs (pquic_fec_batch_recover_span); source symbols
+                                     * they handed over */
 } pquic_fec_batch_stats_t;
 
 /* NULL on failure (bad configuration, no device, out of pinned memory).
@@ -133,6 +135,52 @@ int pquic_fec_batch_generate_window(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx,
 /* Queue fec_recover for `fb` (the receiver's block copy, fec_protoops.h:220-222). */
 int pquic_fec_batch_recover(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t *fb, int xor_scheme,
                             uint64_t now_us, pquic_fec_block_done_fn done, void *user);
+
+/* Span recovery (opt-in, beyond the reference): the joint decode of the sliding-window framework's
+ * overlapping windows (fecgpu_rlc_span_decode, fecgpu.h).  A span is K consecutive symbols of one connection's
+ * stream -- ids base_id .. base_id + K - 1 modulo 2^32 -- with the received ones in src[] and R received repair
+ * symbols, each with the window it protects: repair i covers the nss[i] symbols from stream id first_id[i]
+ * (its fec_scheme_specific field, window_framework_receiver.h:60-86) and is seeded by its own FPID
+ * (rep[i]->fpid.f.source_fpid.raw), as fec_recover seeds every equation.  Every missing column the repairs
+ * determine is recovered, through neighbouring windows where no window alone would do. */
+typedef struct {
+    uint32_t base_id;                    /* stream id of column 0 (ids modulo 2^32) */
+    uint32_t K, R;                       /* 1..128 columns, 1..128 received repairs */
+    pquic_source_symbol_t *const *src;   /* [K], NULL where the symbol is missing */
+    pquic_repair_symbol_t *const *rep;   /* [R], none NULL; seed = its FPID as in fec_recover */
+    const uint32_t *first_id;            /* [R] window start of repair i (fec_scheme_specific) */
+    const uint8_t *nss;                  /* [R] window length of repair i */
+} pquic_fec_span_t;
+/* Called once per accepted span, on the caller's thread.  recovered[c] is the symbol recovered for column c or
+ * NULL; the array is the batcher's and valid during the call, the symbols are the caller's from then on. */
+typedef void (*pquic_fec_span_done_fn)(void *user, const pquic_fec_span_t *sp,
+                                       pquic_source_symbol_t *const *recovered /* [K], NULL where none */,
+                                       uint32_t nrecovered, protoop_arg_t ret);
+/* Queue a span.  The contract is pquic_fec_batch_recover's: the caller keeps `sp`, its arrays and its symbols
+ * alive and unmodified until `done` runs, which happens exactly once, from poll or drain, in flush and
+ * submission order with the other completions.  Column offsets are first_id[i] - base_id modulo 2^32.
+ * Returns -1 -- `done` never runs -- for a NULL argument or table entry, K or R outside 1..128, a repair with
+ * nss == 0 or a window that leaves [0, K), a symbol longer than max_symbol, an allocation failure, and against
+ * an engine library without fecgpu_rlc_span_decode_rows_fused_host.  A span with no missing column completes
+ * inside the call with nothing recovered (stats.immediate).
+ * At submission one source symbol is allocated through the bound allocator for every missing column, so in
+ * the connection's arena: data_length = the span's length (the largest data_length among its repairs; a
+ * received source counts for at most that many bytes), fpid.raw = base_id + column.  The kernel writes the
+ * recovered bytes into them where they lie when they are in a registered heap, as it reads the received rows
+ * there, each for its own length; rows outside every heap go through the job's staging rows and recovered
+ * ones of that kind are copied into their symbols at completion (rows_in_place / rows_staged count both).
+ * At completion the columns of the engine's recovered[] mask are handed over -- a determined source that is
+ * all zero is not, the zero rule of every other path -- and every other pre-allocation is freed first, in
+ * column order, as recover jobs free theirs.  ret is 0 whenever the engine call succeeded: a span whose
+ * repairs determine nothing has nrecovered == 0 and, where it had losses and repairs, counts in
+ * pquic_fec_singular_blocks(); an engine error gives PQUIC_FEC_ERR_UNBOUND as for recover jobs.
+ * Spans of different widths share jobs: a span is padded to its queue's shape, K to 64 or 128 columns (a
+ * padding column is present with length 0 and no repair covers it) and R to 8, 32 or 128 slots (a padding slot
+ * is absent), six queues in all; batch_blocks, max_delay_us, poll_blocks, the provisioner and the small-job
+ * rule apply to them as to recover jobs.  With the engine's knob span_compact (default 1) the data pass skips
+ * every column no unknown depends on, the padding included. */
+int pquic_fec_batch_recover_span(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, const pquic_fec_span_t *sp,
+                                 uint64_t now_us, pquic_fec_span_done_fn done, void *user);
 
 /* Full-rank recovery for the RLC recover jobs of this batcher (on != 0; 0: the reference's elimination, the
  * default).  A full-rank job recovers every block its received repairs determine -- also where the reference

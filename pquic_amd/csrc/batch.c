@@ -41,6 +41,13 @@
  * of copied, the device builds the stream from the rows, and a repair whose symbol lies in an arena is
  * written there by the kernel for the window's length; only symbols outside every arena go through the
  * staging rows, unpadded.
+ * Spans (pquic_fec_batch_recover_span): a span job is a recover job on rows by address whose "blocks" are
+ * spans of one connection's stream, decoded jointly across their overlapping windows by
+ * fecgpu_rlc_span_decode_rows_fused_host (weak as well: without it the call is refused).  Spans of any width
+ * share six queues: a span is padded to its queue's K (64 or 128; a padding column is present, of length 0)
+ * and R (8, 32 or 128; a padding slot is absent).  It always runs on row tables, a heap registered or not:
+ * received rows and the symbols allocated at submission for the missing columns are handed over where they
+ * lie when they are in a heap, and go through the staging rows otherwise.
  * Finished jobs are completed on the caller's thread in poll / drain with the same finish
  * halves the synchronous operations use (fec_core.c), so a batched block ends in exactly the
  * state the protocol operation would leave it in.  The caller keeps a block unmodified until
@@ -91,8 +98,13 @@ static int xor_rows_available(void) {
 #pragma weak fecgpu_rlc_window_encode_rows_host
 static int window_rows_available(void) { return fecgpu_rlc_window_encode_rows_host != NULL; }
 
-enum { OP_GENERATE = 0, OP_RECOVER = 1, OP_WINDOW = 2 /* generate, window blocks */ };
-#define GENERATES(op) ((op) != OP_RECOVER)
+/* And span jobs: without it pquic_fec_batch_recover_span refuses every span. */
+#pragma weak fecgpu_rlc_span_decode_rows_fused_host
+static int span_available(void) { return fecgpu_rlc_span_decode_rows_fused_host != NULL; }
+
+enum { OP_GENERATE = 0, OP_RECOVER = 1, OP_WINDOW = 2 /* generate, window blocks */, OP_SPAN = 3 /* recover, spans */ };
+#define GENERATES(op) ((op) == OP_GENERATE || (op) == OP_WINDOW)
+#define RECOVERS(op) (!GENERATES(op))
 enum { MAX_OPEN = 32, MAX_STAGERS = 16, MAX_ENGINES = 4, STAGE_CHUNK = 256 /* blocks per staging work item */ };
 
 typedef struct {
@@ -103,8 +115,14 @@ typedef struct {
 
 typedef struct {
     picoquic_cnx_t *cnx;
-    pquic_fec_block_t *fb;
-    pquic_fec_block_done_fn done;
+    union {
+        pquic_fec_block_t *fb;
+        const pquic_fec_span_t *span;    /* span jobs */
+    };
+    union {
+        pquic_fec_block_done_fn done;
+        pquic_fec_span_done_fn span_done;  /* span jobs */
+    };
     void *user;
     uint16_t maxl;
     int16_t nalloc;                /* generate: repair symbols allocated at submission */
@@ -154,6 +172,8 @@ typedef struct job {
     size_t rowsym_cap;
     uint64_t nrows;                /* window: stream rows */
     int full;                      /* RLC recover: full-rank mode, the batcher's when the job was flushed */
+    uint8_t *roff, *rnss;          /* span, pinned: [cap][r] column offset / length of each repair's window */
+    size_t win_cap;
 } job_t;
 
 struct pquic_fec_batcher {
@@ -292,6 +312,7 @@ static void job_free(job_t *j) {
     fecgpu_host_free(j->slen);
     fecgpu_host_free(j->rlen);
     fecgpu_host_free(j->blen);
+    fecgpu_host_free(j->roff);
     free(j->pre);
     free(j->cpm);
     free(j->copy);
@@ -344,7 +365,7 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
     const size_t sb = (size_t)cap * k * S, rb = (size_t)cap * r * S;
     /* recover only: the repairs' FPID seeds, [cap][r] (grown on reuse like the repair table) */
     const size_t eb = (size_t)cap * (r ? r : 1) * 4;
-    if (op == OP_RECOVER && j->seed_bytes < eb) {
+    if (RECOVERS(op) && j->seed_bytes < eb) {
         fecgpu_host_free(j->seeds);
         j->seed_bytes = 0;
         if (!(j->seeds = fecgpu_host_alloc(eb))) return -1;
@@ -352,14 +373,15 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
     }
     /* gather tables (generate or recover with a registered heap; XOR where the engine has its row forms):
      * grown on reuse like the repair table */
-    j->gather = (op == OP_WINDOW ? window_rows_available() : !xor_scheme || xor_rows_available()) &&
-                __atomic_load_n(&b->nheaps, __ATOMIC_RELAXED) > 0;
-    if (j->gather && op == OP_RECOVER && j->pre_cap < (size_t)cap * k) {
+    j->gather = op == OP_SPAN ||  /* a span job runs on row tables whatever is registered */
+                ((op == OP_WINDOW ? window_rows_available() : !xor_scheme || xor_rows_available()) &&
+                 __atomic_load_n(&b->nheaps, __ATOMIC_RELAXED) > 0);
+    if (j->gather && RECOVERS(op) && j->pre_cap < (size_t)cap * k) {
         free(j->pre);
         j->pre_cap = (j->pre = calloc((size_t)cap * k, sizeof *j->pre)) ? (size_t)cap * k : 0;
         if (!j->pre) j->gather = 0;
     }
-    if (j->gather && op == OP_RECOVER && !j->cpm && !(j->cpm = malloc(sizeof *j->cpm * 2 * (size_t)cap)))
+    if (j->gather && RECOVERS(op) && !j->cpm && !(j->cpm = malloc(sizeof *j->cpm * 2 * (size_t)cap)))
         j->gather = 0;
     if (j->gather && (j->srow_cap < (size_t)cap * k || j->rrow_cap < (size_t)cap * r || !j->copy)) {
         if (j->srow_cap < (size_t)cap * k) {
@@ -396,6 +418,14 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
     if (j->gather && xor_scheme && !(j->slen && j->rlen && j->blen)) j->gather = 0;
     /* so does the window form: a length per stream row and per window */
     if (j->gather && op == OP_WINDOW && !(j->slen && j->blen)) j->gather = 0;
+    if (op == OP_SPAN) {  /* no staged form: the tables, the lengths and the windows, or no job */
+        if (j->win_cap < (size_t)cap * r) {
+            fecgpu_host_free(j->roff);
+            j->win_cap = (j->roff = fecgpu_host_alloc(2 * (size_t)cap * r)) ? (size_t)cap * r : 0;
+        }
+        if (!j->gather || !j->slen || !j->rlen || !j->blen || !j->roff) return -1;
+        j->rnss = j->roff + (size_t)cap * r;
+    }
     j->ragged = 0;
     j->ncopy = 0;
     if (op == OP_WINDOW) {  /* window tables: start rows (page-locked), the stream's symbols, the grouping */
@@ -533,7 +563,10 @@ static job_t *job_get(pquic_fec_batcher_t *b, int op, int xor_scheme, uint32_t k
 
 static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
     const uint32_t S = j->stride;
-    if (j->op == OP_WINDOW && j->gather)
+    if (j->op == OP_SPAN)
+        j->rc = fecgpu_rlc_span_decode_rows_fused_host(c, j->srow, j->slen, j->rrow, j->rlen, j->blen, j->n, j->k, j->r,
+                                                       S, j->seeds, j->roff, j->rnss, j->sp, j->rp, j->st, j->rec);
+    else if (j->op == OP_WINDOW && j->gather)
         j->rc = fecgpu_rlc_window_encode_rows_host(c, j->srow, j->slen, j->nrows, j->wrow, j->rrow, j->blen, j->n, j->k,
                                                    j->r, S);
     else if (j->op == OP_WINDOW)
@@ -591,7 +624,13 @@ static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
  * it takes the ragged arm, whatever its lengths. */
 static void gather_recover_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1);
 
+static void gather_spans(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1);
+
 static void gather_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1) {
+    if (j->op == OP_SPAN) {
+        gather_spans(b, j, i0, i1);
+        return;
+    }
     if (j->op == OP_RECOVER) {
         gather_recover_blocks(b, j, i0, i1);
         return;
@@ -814,6 +853,81 @@ static void gather_recover_blocks(pquic_fec_batcher_t *b, job_t *j, uint32_t i0,
     }
     pthread_rwlock_unlock(&b->heaps_mu);
     if (ragged) __atomic_store_n(&j->ragged, 1, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&b->stats.rows_in_place, inplace, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&b->stats.rows_staged, staged, __ATOMIC_RELAXED);
+}
+
+/* Span gather: the tables of spans [i0, i1), each padded to the job's k columns and r repair slots.  Every row
+ * counts for its own length: a received source for min(its length, the span's), read where it lies when that
+ * many bytes are in a registered heap, else copied into its staging row; a missing column's row is the symbol
+ * allocated for it at submission when that lies in a heap for the span's length, else its staging row (copied
+ * into the symbol at completion, cpm); a repair likewise, with its seed (its own FPID) and its window.  A
+ * padding column is present with length 0 -- no repair covers it, so its coefficients are zero and the
+ * compacted data pass never lists it -- and a padding slot is absent; both point at their staging rows, which
+ * are never read.  An output row counts once in rows_in_place / rows_staged, like an input row. */
+static void gather_spans(pquic_fec_batcher_t *b, job_t *j, uint32_t i0, uint32_t i1) {
+    const uint32_t S = j->stride, k = j->k, r = j->r;
+    uint64_t inplace = 0, staged = 0;
+    int hint = -1;
+    pthread_rwlock_rdlock(&b->heaps_mu);
+    for (uint32_t i = i0; i < i1; i++) {
+        const entry_t *e = &j->ent[i];
+        const pquic_fec_span_t *s = e->span;
+        uint64_t *sp = j->sp + 2 * (size_t)i, *rp = j->rp + 2 * (size_t)i, *cpm = j->cpm + 2 * (size_t)i;
+        sp[0] = sp[1] = rp[0] = rp[1] = cpm[0] = cpm[1] = 0;
+        j->blen[i] = e->maxl;
+        for (uint32_t x = 0; x < k; x++) {
+            const pquic_source_symbol_t *ss = x < s->K ? s->src[x] : NULL;
+            const size_t o = ((size_t)i * k + x) * S;
+            uint16_t n = 0;
+            uint64_t d = 0;
+            if (ss || x >= s->K) {
+                sp[x >> 6] |= 1ull << (x & 63);
+                if (ss) n = ss->data_length < e->maxl ? ss->data_length : e->maxl;
+                d = n ? heap_dev(b, ss->data, n, &hint) : 0;
+                if (d) {
+                    inplace++;
+                } else if (n) {
+                    memcpy(j->src + o, ss->data, n);
+                    staged++;
+                }
+            } else {
+                const pquic_source_symbol_t *pre = j->pre[(size_t)i * k + x];
+                d = pre ? heap_dev(b, pre->data, e->maxl, &hint) : 0;
+                if (d) {
+                    inplace++;
+                } else {
+                    cpm[x >> 6] |= 1ull << (x & 63);  /* recovered into the staging row */
+                    staged++;
+                }
+            }
+            j->srow[(size_t)i * k + x] = d ? d : j->src_dev + o;
+            j->slen[(size_t)i * k + x] = n;
+        }
+        for (uint32_t x = 0; x < r; x++) {
+            const pquic_repair_symbol_t *rs = x < s->R ? s->rep[x] : NULL;
+            const size_t o = ((size_t)i * r + x) * S, q = (size_t)i * r + x;
+            uint16_t n = 0;
+            uint64_t d = 0;
+            if (rs) {
+                rp[x >> 6] |= 1ull << (x & 63);
+                n = rs->data_length;  /* at most the span's length, which is the largest of them */
+                d = n ? heap_dev(b, rs->data, n, &hint) : 0;
+                if (d) {
+                    inplace++;
+                } else if (n) {
+                    memcpy(j->rep + o, rs->data, n);
+                    staged++;
+                }
+            }
+            j->rrow[q] = d ? d : j->rep_dev + o;
+            j->rlen[q] = n;
+            j->seeds[q] = rs ? rs->fpid.f.source_fpid.raw : 0;
+            j->roff[q] = rs ? (uint8_t)(s->first_id[x] - s->base_id) : 0;
+            j->rnss[q] = rs ? s->nss[x] : 0;
+        }
+    }
+    pthread_rwlock_unlock(&b->heaps_mu);
     __atomic_fetch_add(&b->stats.rows_in_place, inplace, __ATOMIC_RELAXED);
     __atomic_fetch_add(&b->stats.rows_staged, staged, __ATOMIC_RELAXED);
 }
@@ -1263,7 +1377,7 @@ static int submit(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t
     if (!j) return -1;
     const uint32_t i = j->n;
     j->fbn[i] = fb->fec_block_number & 0xffffffu;  /* rows are copied later, by a stager */
-    j->ent[i] = (entry_t){cnx, fb, done, user, maxl, -1};
+    j->ent[i] = (entry_t){.cnx = cnx, .fb = fb, .done = done, .user = user, .maxl = maxl, .nalloc = -1};
     if (GENERATES(op))  /* the protocol operation's allocations, in its order, on this thread */
         j->ent[i].nalloc = (int16_t)fec_generate_alloc(cnx, fb, maxl, j->reps + (size_t)i * r);
     else if (j->gather && xor_scheme)  /* the one recovered symbol, so the kernel writes it where it will stay */
@@ -1301,6 +1415,62 @@ int pquic_fec_batch_recover(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_f
     return submit(b, cnx, fb, OP_RECOVER, xor_scheme ? 1 : 0, now_us, done, user);
 }
 
+/* The queue shapes of span jobs: K padded to 64 or 128 columns, R to 8, 32 or 128 slots. */
+static uint32_t span_kc(uint32_t K) { return K <= 64 ? 64 : 128; }
+static uint32_t span_rc(uint32_t R) { return R <= 8 ? 8 : R <= 32 ? 32 : 128; }
+
+/* what a span completion with nothing recovered hands over as recovered[] */
+static pquic_source_symbol_t *const g_no_symbols[FECGPU_MAX_K];
+
+int pquic_fec_batch_recover_span(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, const pquic_fec_span_t *sp,
+                                 uint64_t now_us, pquic_fec_span_done_fn done, void *user) {
+    if (!b || !sp || !done || !span_available()) return -1;
+    if (sp->K < 1 || sp->K > FECGPU_MAX_K || sp->R < 1 || sp->R > FECGPU_MAX_R) return -1;
+    if (!sp->src || !sp->rep || !sp->first_id || !sp->nss) return -1;
+    uint16_t maxl = 0;  /* the span's length: the longest repair */
+    for (uint32_t i = 0; i < sp->R; i++) {
+        const pquic_repair_symbol_t *rs = sp->rep[i];
+        const uint32_t off = sp->first_id[i] - sp->base_id;  /* modulo 2^32 */
+        if (!rs || (rs->data_length && !rs->data) || rs->data_length > b->cfg.max_symbol) return -1;
+        if (!sp->nss[i] || off >= sp->K || sp->nss[i] > sp->K - off) return -1;
+        if (rs->data_length > maxl) maxl = rs->data_length;
+    }
+    uint32_t missing = 0;
+    for (uint32_t x = 0; x < sp->K; x++) {
+        const pquic_source_symbol_t *ss = sp->src[x];
+        if (!ss) missing++;
+        else if ((ss->data_length && !ss->data) || ss->data_length > b->cfg.max_symbol) return -1;
+    }
+    if (!g_fec_bound) {
+        b->stats.immediate++;
+        done(user, sp, g_no_symbols, 0, PQUIC_FEC_ERR_UNBOUND);
+        return 0;
+    }
+    if (!missing || !maxl) {  /* nothing to recover, or nothing to recover it from */
+        b->stats.immediate++;
+        done(user, sp, g_no_symbols, 0, 0);
+        return 0;
+    }
+    int slot;
+    job_t *j = open_job(b, OP_SPAN, 0, span_kc(sp->K), span_rc(sp->R), &slot);
+    if (!j) return -1;
+    const uint32_t i = j->n;
+    j->ent[i] = (entry_t){.cnx = cnx, .span = sp, .span_done = done, .user = user, .maxl = maxl, .nalloc = -1};
+    /* the recovered symbols, allocated here -- on this thread, in the connection's arena -- so the kernel
+     * writes them where they will stay; numbered by stream id */
+    pquic_source_symbol_t **pre = j->pre + (size_t)i * j->k;
+    for (uint32_t x = 0; x < j->k; x++)
+        pre[x] = x < sp->K && !sp->src[x] ? fec_new_source(cnx, sp->base_id + x, maxl) : NULL;
+    if (!i) {
+        j->t_first = now_us;
+        if (now_us < b->next_due) b->next_due = now_us;
+    }
+    j->n = i + 1;
+    b->stats.submitted++;
+    if (j->n == j->cap) flush_job(b, slot, &b->stats.flushed_full);
+    return 0;
+}
+
 /* The symbols a completion hands to the framework -- a generate's repairs, a gathered recover's
  * recovered sources -- are what the framework touches next (it sends their bytes, then frees them; the
  * plugin allocator reads the slot header just before the data, picoquic/memory.c:123-127).  The kernel
@@ -1314,7 +1484,7 @@ static void prefetch_range(const void *p, size_t n) {
 }
 
 static void prefetch_syms(const job_t *j, uint32_t i, int data) {
-    if (data) {  /* the block's symbol pointers the completion writes (and the framework then reads) */
+    if (data && j->op != OP_SPAN) {  /* the block's symbol pointers the completion writes (and the framework then reads) */
         pquic_fec_block_t *fb = j->ent[i].fb;
         if (GENERATES(j->op))
             prefetch_range(&fb->repair_symbols[0], sizeof fb->repair_symbols[0] * (j->ent[i].nalloc > 0 ? j->ent[i].nalloc : 1));
@@ -1352,6 +1522,46 @@ static void prefetch_syms(const job_t *j, uint32_t i, int data) {
             }
         }
     }
+}
+
+/* Completion of span i of a finished span job: as fec_recover_finish_pre completes a block.  The symbols
+ * allocated for columns the engine did not recover (all of them after an engine error) are freed first, in
+ * column order; then every recovered column's symbol is handed over -- after copying the span's length from
+ * the staging row where the kernel wrote there (cpm), into a symbol allocated now where the allocation at
+ * submission had failed (skipped when that fails too).  pre[] becomes the recovered[] the callback sees. */
+static void span_finish(pquic_fec_batcher_t *b, job_t *j, uint32_t i, uint64_t *nrec_acc) {
+    const entry_t *e = &j->ent[i];
+    const pquic_fec_span_t *s = e->span;
+    const uint32_t S = j->stride;
+    pquic_source_symbol_t **pre = j->pre + (size_t)i * j->k;
+    const uint64_t *rec = j->rec + 2 * (size_t)i, *cpm = j->cpm + 2 * (size_t)i;
+    const int ok = !j->rc && j->st[i] == FECGPU_BLOCK_RECOVERED;
+    if (j->rc) FEC_STAT_ADD(errors, 1);
+    else if (j->st[i] == FECGPU_BLOCK_SINGULAR) __atomic_fetch_add(&g_fec_singular_blocks, 1, __ATOMIC_RELAXED);
+    for (uint32_t x = 0; x < s->K; x++) {
+        if ((ok && ((rec[x >> 6] >> (x & 63)) & 1)) || !pre[x]) continue;
+        g_fec_api.my_free(e->cnx, pre[x]->data);
+        g_fec_api.my_free(e->cnx, pre[x]);
+        pre[x] = NULL;
+    }
+    uint32_t nrec = 0;
+    for (uint32_t x = 0; ok && x < s->K; x++) {
+        if (!((rec[x >> 6] >> (x & 63)) & 1) || s->src[x]) continue;
+        const uint8_t *row = j->src + ((size_t)i * j->k + x) * S;
+        if (!pre[x]) {
+            if (!(pre[x] = fec_new_source(e->cnx, s->base_id + x, e->maxl))) continue;
+            memcpy(pre[x]->data, row, e->maxl);
+        } else if ((cpm[x >> 6] >> (x & 63)) & 1) {
+            memcpy(pre[x]->data, row, e->maxl);
+        }
+        nrec++;
+    }
+    *nrec_acc += nrec;
+    if (!j->rc) {
+        b->stats.spans++;
+        b->stats.span_symbols += nrec;
+    }
+    e->span_done(e->user, s, pre, nrec, j->rc ? PQUIC_FEC_ERR_UNBOUND : 0);
 }
 
 /* Completes finished jobs, at most `budget` blocks (0: all): the finish halves of the protocol
@@ -1407,7 +1617,12 @@ static int collect(pquic_fec_batcher_t *b, uint32_t budget) {
             }
             protoop_arg_t ret;
             pquic_repair_symbol_t **reps = GENERATES(j->op) ? j->reps + (size_t)i * j->r : NULL;
-            pquic_source_symbol_t **pre = j->op == OP_RECOVER && j->gather ? j->pre + (size_t)i * j->k : NULL;
+            pquic_source_symbol_t **pre = RECOVERS(j->op) && j->gather ? j->pre + (size_t)i * j->k : NULL;
+            if (j->op == OP_SPAN) {
+                span_finish(b, j, i, &nrec);
+                n++;
+                continue;
+            }
             if (j->rc) {
                 FEC_STAT_ADD(errors, 1);
                 ret = PQUIC_FEC_ERR_UNBOUND;

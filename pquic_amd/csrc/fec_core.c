@@ -40,6 +40,10 @@ static pquic_source_symbol_t *new_source(picoquic_cnx_t *cnx, uint32_t fpid_raw,
     return s;
 }
 
+pquic_source_symbol_t *fec_new_source(picoquic_cnx_t *cnx, uint32_t fpid_raw, uint16_t len) {
+    return new_source(cnx, fpid_raw, len);
+}
+
 int fec_generate_check(const pquic_fec_block_t *fb, int xor_scheme, uint16_t *maxl) {
     const int k = fb->total_source_symbols, r = fb->total_repair_symbols;
     /* rlc_fec_scheme_generate_gf256.c:34-39 / xor_fec_scheme_generate.c:45-50 */

@@ -90,6 +90,11 @@ protoop_arg_t fec_recover_finish_pre(picoquic_cnx_t *cnx, pquic_fec_block_t *fb,
                                      pquic_source_symbol_t *const *pre, const uint64_t copy[2], const uint8_t *src_rows,
                                      uint32_t stride, uint16_t maxl, uint64_t *nrec_acc);
 
+/* One source symbol of len bytes (data unwritten) with FPID fpid_raw from the bound allocator, as
+ * malloc_source_symbol makes it (fec.h:201-214), or NULL: the span jobs of the batching adapter allocate the
+ * symbols of a span's missing columns with it, numbered by stream id. */
+pquic_source_symbol_t *fec_new_source(picoquic_cnx_t *cnx, uint32_t fpid_raw, uint16_t len);
+
 /* The XOR counterparts (the batcher's XOR gather jobs).  fec_recover_alloc_xor allocates one symbol of maxl
  * bytes for the LAST missing source j -- the one xor_fec_scheme.c:54-58 recovers -- with the XOR branch's
  * FPID, (fec_block_number << 8) | j, into pre[j]; every other pre[] entry is NULL.  Returns how many it got

@@ -132,7 +132,10 @@ static bool ring_ok(int v) { return v == 0 || v == 2; }
   X(YIELD_ALWAYS, "yield_always", 0, 0, 1, nullptr)                                                             \
   /* the hooks count as in use for this long after a request (tests lengthen it so that slicing does not      \
      depend on how quickly the call follows the hook) */                                                       \
-  X(YIELD_WINDOW_MS, "yield_window_ms", 100, 0, 600000, nullptr)
+  X(YIELD_WINDOW_MS, "yield_window_ms", 100, 0, 600000, nullptr)                                               \
+  /* span decode's data pass (register-prefetch recover kernels): a tile's setup lists only the inputs with a  \
+     non-zero coefficient for one of its unknowns (1) or all k of the span (0); the LDS-ring tiles keep all k */\
+  X(SPAN_COMPACT, "span_compact", 1, 0, 1, nullptr)
 
 #define X(id, name, def, lo, hi, ok) K_##id,
 enum KnobId { FEC_KNOBS(X) K_N };
@@ -1715,6 +1718,7 @@ __global__ __launch_bounds__(64) void k_rlc_plan_tile(uint64_t nblocks, int k, i
 // per-block decode record in LDS (layout shared with gen_bitslice.py): 16 output addresses |
 // ws non-zero-flag address @128 | rt @136 | non-zero flags @144 (written by the asm body)
 constexpr int kDecRec = 160, kDecRecNzPtr = 16, kDecRecRt = 34, kDecRecNz = 144;
+constexpr int kDecRecKc = 35;  // u32 the bodies do not read: in a group's first record, its table entries per block
 
 // The reference's zero/undetermined rule (rlc_fec_scheme_gf256.c:98-101, 218-236) for one block,
 // given its non-zero flags: unknown u is inserted iff it is non-zero and every unknown its row
@@ -2033,12 +2037,12 @@ __device__ __forceinline__ uint64_t rec_row(uint64_t b, int k, int j, int dst_ro
 // its own length -- an input for min(its length, blk_len[b]), an output for blk_len[b] bytes, both
 // clamped to L -- through the length-aware bodies.
 template <int RT, int VEC, bool LEN = false>
-__device__ void recover_bs_group(uint64_t q, uint64_t NG, uint64_t bstep, uint8_t *__restrict__ src,
+__device__ __forceinline__ void recover_bs_group(uint64_t q, uint64_t NG, uint64_t bstep, uint8_t *__restrict__ src,
                                  const uint8_t *__restrict__ rep, uint64_t nblocks, int k, int r, int L, int nchunks,
                                  int chunk_bytes, uint8_t *ws, int r0, int G, uint8_t *status, uint64_t *recovered,
                                  int ilv, uint8_t *dst, uint8_t *lds, uint8_t *wsl = nullptr, int dst_rows = 0,
                                  const uint32_t *src_len = nullptr, const uint32_t *rep_len = nullptr,
-                                 const uint32_t *blk_len = nullptr) {
+                                 const uint32_t *blk_len = nullptr, uint8_t *cmp = nullptr) {
   const WsLayout WL = ws_layout((uint32_t)k, (uint32_t)r);
   const int lane = threadIdx.x;
   RecoverLds<RT> S(lds, G, k);
@@ -2089,9 +2093,59 @@ __device__ void recover_bs_group(uint64_t q, uint64_t NG, uint64_t bstep, uint8_
       S.ecnt[t] = (uint8_t)(e - r0 < RT ? e - r0 : RT);
     }
     __syncthreads();
-    // coefficient rows and input addresses, one (block, input j) pair per lane
-    for (int x = lane; x < nact * k; x += 64) {
-      const int t = x / k, j = x - t * k;
+    int kc = k;  // table entries per active block
+    if (cmp) {
+      // Compacted setup (span records, knob span_compact): per active block only the inputs whose coefficient
+      // is non-zero for a live unknown of the tile, in ascending slot order.  The lanes walk the (block, input)
+      // pairs as the full setup does; a ballot and a prefix popcount over the lanes of the same block give an
+      // input's place in its block's list (cl, [G][k] slots; cnt, the lists' lengths so far).  Blocks with
+      // fewer entries than the group's longest list, kc, are padded below.
+      uint8_t *cnt = cmp, *cl = cmp + 80;
+      if (lane < nact) cnt[lane] = 0;
+      __syncthreads();
+      for (int x0 = 0; x0 < nact * k; x0 += 64) {
+        const int x = x0 + lane;
+        const bool in = x < nact * k;
+        const int t = in ? x / k : 0, j = x - t * k;
+        const int lo = t * k - x0 > 0 ? t * k - x0 : 0, hi = (t + 1) * k - x0;  // lanes of block t: [lo, hi)
+        const uint64_t seg = in ? (hi >= 64 ? ~0ull : (1ull << hi) - 1) & ~((1ull << lo) - 1) : 0ull;
+        bool nzr = false;
+        if (in) {
+          const int rt = S.ecnt[t];
+          const uint8_t *h = recg(S.gid[t]);
+#pragma unroll
+          for (int u = 0; u < RT; u++) nzr |= u < rt && h[WL.off_D + (r0 + u) * k + j] != 0;
+        }
+        const uint64_t m = __ballot(nzr) & seg;
+        const int base = in ? cnt[t] : 0;
+        if (nzr) cl[t * k + base + __popcll(m & ((1ull << lane) - 1))] = (uint8_t)j;
+        __syncthreads();
+        if (in && lane == lo) cnt[t] = (uint8_t)(base + __popcll(m));
+        __syncthreads();
+      }
+      int c = lane < nact ? cnt[lane] : 0;
+#pragma unroll
+      for (int o = 32; o; o >>= 1) {
+        const int d = __shfl_xor(c, o);
+        c = d > c ? d : c;
+      }
+      kc = __builtin_amdgcn_readfirstlane(c > 1 ? c : 1);
+    }
+    // kc waits in LDS (a free word of the first record) for the data pass, which reads it back: the compacted
+    // setup leaves nothing new in a register across the asm bodies
+    if (lane == 0) reinterpret_cast<uint32_t *>(S.rec)[kDecRecKc] = (uint32_t)kc;
+    // coefficient rows and input addresses, one table entry per lane: input j of active block t, or (compacted
+    // setup) a padding entry -- coefficient 0 in every field; length 0 in the length-aware form, else the
+    // address of a row the block reads anyway
+    for (int x = lane; x < nact * kc; x += 64) {
+      const int t = x / kc;
+      int j = x - t * kc;
+      bool live = true;
+      if (cmp) {
+        const int n = cmp[t];
+        live = j < n;
+        j = n ? cmp[80 + t * k + (live ? j : 0)] : 0;
+      }
       const uint64_t b = b0 + S.gid[t] * bstep;
       const int rt = S.ecnt[t];
       const uint8_t *h = recg(S.gid[t]);
@@ -2111,14 +2165,15 @@ __device__ void recover_bs_group(uint64_t q, uint64_t NG, uint64_t bstep, uint8_
 #else
 #pragma unroll
       for (int u = 0; u < NF; u++)  // case offset of D[u][j]; 0 past the live unknowns ends the chain
-        row[FEC_BS_FIELD_SLOT(RT, u)] = (u < rt) ? FEC_BS_FIELD(h[WL.off_D + (r0 + u) * k + j], u) : (uint16_t)0;
+        row[FEC_BS_FIELD_SLOT(RT, u)] =
+            (live && u < rt) ? FEC_BS_FIELD(h[WL.off_D + (r0 + u) * k + j], u) : (uint16_t)0;
 #endif
       const uint32_t sl = h[WL.off_slot + j];
 #endif
       if constexpr (LEN) {
         const uint32_t bl = min_u32(blk_len[b], (uint32_t)L);
         const uint64_t ri = (sl & 0x80) ? b * (uint64_t)r + (sl & 0x7f) : b * (uint64_t)k + sl;
-        const uint32_t n = min_u32((sl & 0x80) ? rep_len[ri] : src_len[ri], bl);
+        const uint32_t n = live ? min_u32((sl & 0x80) ? rep_len[ri] : src_len[ri], bl) : 0u;
         S.intab[x] = row_entry(reinterpret_cast<const uint64_t *>((sl & 0x80) ? rep : src)[ri], n);
       } else if (dst_rows < 0) {  // row tables: src / rep hold the rows' device addresses ([block][k] / [block][r])
         S.intab[x] = (sl & 0x80) ? reinterpret_cast<const uint64_t *>(rep)[b * (uint64_t)r + (sl & 0x7f)]
@@ -2177,8 +2232,9 @@ __device__ void recover_bs_group(uint64_t q, uint64_t NG, uint64_t bstep, uint8_
         // nsrc and k go to SGPRs: readfirstlane states their uniformity (a plan inlined into a
         // one-lane branch before this call can leave the compiler unsure of it)
         if (lane < ln.active) {
-          const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane(nact * k);
-          const uint32_t ku = (uint32_t)__builtin_amdgcn_readfirstlane(k);
+          const uint32_t ku =
+              (uint32_t)__builtin_amdgcn_readfirstlane(reinterpret_cast<const uint32_t *>(S.rec)[kDecRecKc]);
+          const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane(nact) * ku;
           if constexpr (LEN) bs_decl_call<RT, VEC>(lds_addr(S.intab), lds_addr(S.rec), ns, ku, lds_addr(S.coef), ln);
           else bs_dec_call<RT, VEC>(lds_addr(S.intab), lds_addr(S.rec), ns, ku, lds_addr(S.coef), ln);
         }
@@ -2228,7 +2284,8 @@ void k_rlc_recover_bs(uint8_t *__restrict__ src, const uint8_t *__restrict__ rep
                                                        uint64_t nblocks, int k, int r, int L, int nchunks,
                                                        int chunk_bytes, uint8_t *ws, int r0, int G,
                                                        uint8_t *status, uint64_t *recovered, int ilv,
-                                                       uint8_t *dst, uint32_t wsl_off, int dst_rows, uint64_t q0) {
+                                                       uint8_t *dst, uint32_t wsl_off, int dst_rows,
+                                                       uint32_t cmp_off, uint64_t q0) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const uint64_t NG = (nblocks + G - 1) / G;  // groups; interleaved as in k_rlc_encode_bs
   const uint64_t bstep = (ilv & 1) ? NG : 1;
@@ -2238,7 +2295,8 @@ void k_rlc_recover_bs(uint8_t *__restrict__ src, const uint8_t *__restrict__ rep
   const uint64_t q = q0 + grp_index(ilv);
   if (q < NG)
     recover_bs_group<RT, VEC>(q, NG, bstep, src, rep, nblocks, k, r, L, nchunks, chunk_bytes, ws, r0, G, status,
-                              recovered, ilv, dst, lds, wsl_off ? lds + wsl_off : nullptr, dst_rows);
+                              recovered, ilv, dst, lds, wsl_off ? lds + wsl_off : nullptr, dst_rows, nullptr, nullptr,
+                              nullptr, cmp_off ? lds + cmp_off : nullptr);
 }
 
 // The recover pass of fecgpu_rlc_decode_rows_fused: row tables and a length per row, one group per workgroup
@@ -2247,7 +2305,7 @@ __global__ __launch_bounds__(64) void k_rlc_recover_rows_fused(
     uint8_t *__restrict__ src_rows, const uint8_t *__restrict__ rep_rows, const uint32_t *__restrict__ src_len,
     const uint32_t *__restrict__ rep_len, const uint32_t *__restrict__ blk_len, uint64_t nblocks, int k, int r, int L,
     int nchunks, int chunk_bytes, uint8_t *ws, int r0, int G, uint8_t *status, uint64_t *recovered, int ilv,
-    uint32_t wsl_off, uint64_t q0) {
+    uint32_t wsl_off, uint32_t cmp_off, uint64_t q0) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const uint64_t NG = (nblocks + G - 1) / G;
   const uint64_t bstep = (ilv & 1) ? NG : 1;
@@ -2255,7 +2313,7 @@ __global__ __launch_bounds__(64) void k_rlc_recover_rows_fused(
   if (q < NG)
     recover_bs_group<RT, VEC, true>(q, NG, bstep, src_rows, rep_rows, nblocks, k, r, L, nchunks, chunk_bytes, ws, r0, G,
                                     status, recovered, ilv, nullptr, lds, wsl_off ? lds + wsl_off : nullptr, -1,
-                                    src_len, rep_len, blk_len);
+                                    src_len, rep_len, blk_len, cmp_off ? lds + cmp_off : nullptr);
 }
 
 // Encode with the rows given by address (fecgpu_rlc_encode_rows): the batching adapter hands the
@@ -2941,10 +2999,11 @@ static void launch_encode_bs(const uint8_t *src, uint8_t *rep, uint64_t nb, int 
 }
 
 // Launch shape of a recover data pass (k_rlc_recover_bs, k_rlc_recover_rows_fused): blocks per group, groups,
-// dynamic LDS, and where in it the group's workspace records are staged (0: not staged)
-struct RecoverShape { int G; uint64_t groups; size_t lds; uint32_t wsl_off; };
+// dynamic LDS, where in it the group's workspace records are staged (0: not staged), and where the compacted
+// setup keeps its input lists (0: the full setup; 64 list lengths, the longest, then [G][k] slots from byte 80)
+struct RecoverShape { int G; uint64_t groups; size_t lds; uint32_t wsl_off, cmp_off; };
 template <int RT>
-static RecoverShape recover_shape(uint64_t nb, int k, int r, const BsCfg &c, const uint8_t *ws) {
+static RecoverShape recover_shape(uint64_t nb, int k, int r, const BsCfg &c, const uint8_t *ws, bool compact) {
   RecoverShape h;
   h.G = bs_group(RT, k, FEC_BS_COEF_ROW_BYTES(RT) + 8, kDecRec + 80, false, c.nchunks, nb);
   h.lds = RecoverLds<RT>::bytes(h.G, k);
@@ -2954,6 +3013,11 @@ static RecoverShape recover_shape(uint64_t nb, int k, int r, const BsCfg &c, con
   if (knob(K_WS_LDS) && wsb <= kWsLdsMax && ((uintptr_t)ws & 15) == 0) {
     h.wsl_off = (uint32_t)((h.lds + 15) & ~(size_t)15);
     h.lds = h.wsl_off + wsb;
+  }
+  h.cmp_off = 0;
+  if (compact) {
+    h.cmp_off = (uint32_t)((h.lds + 15) & ~(size_t)15);
+    h.lds = h.cmp_off + 80 + (size_t)h.G * k;
   }
   h.groups = (nb + h.G - 1) / h.G;
   // knob dec_waves = n: at most n waves per SIMD (the workgroup's LDS sized so 4 n fit a CU's 160 KiB)
@@ -2967,10 +3031,11 @@ static RecoverShape recover_shape(uint64_t nb, int k, int r, const BsCfg &c, con
 template <int RT, int VEC>
 static void launch_recover_bs(uint8_t *src, const uint8_t *rep, uint64_t nb, int k, int r, int L, const BsCfg &c,
                               uint8_t *ws, int r0, uint8_t *status, uint64_t *recovered, hipStream_t s,
-                              uint8_t *dst, int dst_rows) {
-  const RecoverShape h = recover_shape<RT>(nb, k, r, c, ws);
+                              uint8_t *dst, int dst_rows, bool compact) {
+  const RecoverShape h = recover_shape<RT>(nb, k, r, c, ws, compact);
   FEC_LAUNCH_GROUPS((k_rlc_recover_bs<RT, VEC>), h.groups, 64, h.lds, s, src, rep, nb, k, r, L, c.nchunks,
-                    c.chunk_bytes, ws, r0, h.G, status, recovered, interleave_groups(), dst, h.wsl_off, dst_rows)
+                    c.chunk_bytes, ws, r0, h.G, status, recovered, interleave_groups(), dst, h.wsl_off, dst_rows,
+                    h.cmp_off)
 }
 
 template <int RT, int VEC>
@@ -2996,11 +3061,11 @@ template <int RT, int VEC>
 static void launch_recover_rows_fused(const uint64_t *src_rows, const uint64_t *rep_rows, const uint32_t *src_len,
                                       const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nb, int k, int r,
                                       int L, const BsCfg &c, uint8_t *ws, int r0, uint8_t *status,
-                                      uint64_t *recovered, hipStream_t s) {
-  const RecoverShape h = recover_shape<RT>(nb, k, r, c, ws);
+                                      uint64_t *recovered, hipStream_t s, bool compact) {
+  const RecoverShape h = recover_shape<RT>(nb, k, r, c, ws, compact);
   FEC_LAUNCH_GROUPS((k_rlc_recover_rows_fused<RT, VEC>), h.groups, 64, h.lds, s, (uint8_t *)src_rows,
                     (const uint8_t *)rep_rows, src_len, rep_len, blk_len, nb, k, r, L, c.nchunks, c.chunk_bytes, ws, r0,
-                    h.G, status, recovered, interleave_groups(), h.wsl_off)
+                    h.G, status, recovered, interleave_groups(), h.wsl_off, h.cmp_off)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4450,6 +4515,15 @@ static int decode_args(const void *src, const void *rep, uint64_t nblocks, uint3
 // (profiles/r02_plan_crossover_wreg.log).
 constexpr uint64_t kPlanWaveMaxBlocks = 4096;
 
+// The workspace the last fecgpu_rlc_span_decode_plan filled: the apply calls that follow it on that workspace
+// take the compacted setup (knob span_compact).  A reference or full-rank plan into the same workspace clears
+// it.  A caller planning spans into several workspaces at once gets the full setup for all but the last,
+// which costs time and changes no byte.
+static std::atomic<uintptr_t> g_span_ws{0};
+static inline bool span_planned(const void *workspace) {
+  return workspace && g_span_ws.load(std::memory_order_relaxed) == (uintptr_t)workspace;
+}
+
 static int decode_plan_impl(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t fbn_base, const uint32_t *fbn,
                             const uint32_t *seeds, const uint64_t *src_present, const uint64_t *rep_present,
                             void *workspace, size_t workspace_bytes, void *stream) {
@@ -4457,6 +4531,7 @@ static int decode_plan_impl(uint64_t nblocks, uint32_t k, uint32_t r, uint32_t f
   int rc = decode_args(&dummy, &dummy, nblocks, k, r, 4, src_present, rep_present, &dummy, &dummy, workspace,
                        workspace_bytes);
   if (rc || nblocks == 0) return rc;
+  if (span_planned(workspace)) g_span_ws.store(0, std::memory_order_relaxed);
   hipStream_t s = (hipStream_t)stream;
   uint8_t *ws = (uint8_t *)workspace;
   const size_t lane_lds = plan_lane_lds(k, r);
@@ -4600,8 +4675,11 @@ int fecgpu_rlc_span_decode_plan(uint64_t nspans, uint32_t k, uint32_t r, const u
   int rc = span_plan_args(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace,
                           workspace_bytes);
   if (rc || nspans == 0) return rc;
-  return span_plan_launch(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace,
-                          (hipStream_t)stream);
+  if ((rc = span_plan_launch(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace,
+                             (hipStream_t)stream)))
+    return rc;
+  g_span_ws.store((uintptr_t)workspace, std::memory_order_relaxed);
+  return FECGPU_OK;
 }
 
 static int launch_finalize(uint64_t nblocks, uint32_t k, uint32_t r, uint8_t *status, uint64_t *recovered,
@@ -4616,7 +4694,8 @@ static int launch_finalize(uint64_t nblocks, uint32_t k, uint32_t r, uint8_t *st
 // is the in-place form).  Inputs are only ever read from src/rep, outputs only written to dst.
 static int decode_apply_impl(const void *src, const void *rep, void *dst, uint64_t nblocks, uint32_t k,
                              uint32_t r, uint32_t symbol_size, uint8_t *status, uint64_t *recovered,
-                             void *workspace, size_t workspace_bytes, hipStream_t s, int dst_rows = 0) {
+                             void *workspace, size_t workspace_bytes, hipStream_t s, int dst_rows = 0,
+                             bool span = false) {
   static const uint64_t dummy = 0;
   int rc = decode_args(src, rep, nblocks, k, r, symbol_size, &dummy, &dummy, status, recovered, workspace,
                        workspace_bytes);
@@ -4632,6 +4711,7 @@ static int decode_apply_impl(const void *src, const void *rep, void *dst, uint64
   const BsCfg cfg = pick_bs_cfg((int)symbol_size);
   const bool fused = (int)L.em <= rt;  // one pass covers every unknown of every block
   const bool ring = use_ring(rt, k, cfg, false);
+  const bool compact = span && knob(K_SPAN_COMPACT);  // span records: the compacted setup (not the ring's)
   for (int r0 = 0; r0 < (int)L.em; r0 += rt) {
     if (ring) {
       launch_recover_bs2<16>((uint8_t *)src, (const uint8_t *)rep, nblocks, (int)k, (int)r, (int)symbol_size, cfg,
@@ -4640,7 +4720,7 @@ static int decode_apply_impl(const void *src, const void *rep, void *dst, uint64
     } else {
       FEC_BS_DISPATCH(launch_recover_bs, (uint8_t *)src, (const uint8_t *)rep, nblocks, (int)k, (int)r,
                       (int)symbol_size, cfg, ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s,
-                      (uint8_t *)dst, dst_rows)
+                      (uint8_t *)dst, dst_rows, compact)
     }
   }
   HIPCHK(hipGetLastError());
@@ -4651,14 +4731,14 @@ int fecgpu_rlc_decode_apply(void *src, const void *rep, uint64_t nblocks, uint32
                             uint32_t symbol_size, uint8_t *status, uint64_t *recovered, void *workspace,
                             size_t workspace_bytes, void *stream) {
   return decode_apply_impl(src, rep, src, nblocks, k, r, symbol_size, status, recovered, workspace,
-                           workspace_bytes, (hipStream_t)stream);
+                           workspace_bytes, (hipStream_t)stream, 0, span_planned(workspace));
 }
 
 int fecgpu_rlc_decode_apply_to(const void *src, const void *rep, void *dst, uint64_t nblocks, uint32_t k,
                                uint32_t r, uint32_t symbol_size, uint8_t *status, uint64_t *recovered,
                                void *workspace, size_t workspace_bytes, void *stream) {
   return decode_apply_impl(src, rep, dst, nblocks, k, r, symbol_size, status, recovered, workspace,
-                           workspace_bytes, (hipStream_t)stream);
+                           workspace_bytes, (hipStream_t)stream, 0, span_planned(workspace));
 }
 
 int fecgpu_rlc_decode_apply_packed(const void *src, const void *rep, void *dst, uint64_t nblocks, uint32_t k,
@@ -4666,7 +4746,7 @@ int fecgpu_rlc_decode_apply_packed(const void *src, const void *rep, void *dst, 
                                    void *workspace, size_t workspace_bytes, void *stream) {
   const uint32_t em = k < r ? k : r;
   return decode_apply_impl(src, rep, dst, nblocks, k, r, symbol_size, status, recovered, workspace,
-                           workspace_bytes, (hipStream_t)stream, em ? (int)em : 1);
+                           workspace_bytes, (hipStream_t)stream, em ? (int)em : 1, span_planned(workspace));
 }
 
 // full != 0: full-rank mode.  Its plan names only the repairs it selected and a singular block has
@@ -4697,7 +4777,7 @@ extern "C" __attribute__((visibility("hidden"))) int fecgpu_rlc_decode_rows_inte
   for (int r0 = 0; r0 < (int)WL.em; r0 += rt) {
     FEC_BS_DISPATCH(launch_recover_bs, (uint8_t *)src_rows, (const uint8_t *)rep_rows, nblocks, (int)k, (int)r,
                     (int)symbol_size, cfg, ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s,
-                    (uint8_t *)nullptr, -1)
+                    (uint8_t *)nullptr, -1, false)
   }
   HIPCHK(hipGetLastError());
   return fused ? FECGPU_OK : launch_finalize(nblocks, k, r, status, recovered, ws, s);
@@ -4969,7 +5049,7 @@ int fecgpu_rlc_encode_rows_fused(const uint64_t *src_rows, const uint32_t *src_l
 static int decode_rows_fused_pass(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
                                   const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nblocks, uint32_t k,
                                   uint32_t r, uint32_t symbol_size, uint8_t *status, uint64_t *recovered, uint8_t *ws,
-                                  hipStream_t s) {
+                                  hipStream_t s, bool span = false) {
   count_decode(nblocks);
   const WsLayout WL = ws_layout(k, r);
   if (r == 0) return launch_finalize(nblocks, k, r, status, recovered, ws, s);
@@ -4977,9 +5057,10 @@ static int decode_rows_fused_pass(const uint64_t *src_rows, const uint32_t *src_
   const int rt = decode_tile(WL.em);
   const BsCfg cfg = pick_bs_cfg((int)symbol_size);
   const bool fused = (int)WL.em <= rt;
+  const bool compact = span && knob(K_SPAN_COMPACT);  // span records: the compacted setup
   for (int r0 = 0; r0 < (int)WL.em; r0 += rt) {
     FEC_BS_DISPATCH(launch_recover_rows_fused, src_rows, rep_rows, src_len, rep_len, blk_len, nblocks, (int)k, (int)r,
-                    (int)symbol_size, cfg, ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s)
+                    (int)symbol_size, cfg, ws, r0, fused ? status : nullptr, fused ? recovered : nullptr, s, compact)
   }
   HIPCHK(hipGetLastError());
   return fused ? FECGPU_OK : launch_finalize(nblocks, k, r, status, recovered, ws, s);
@@ -5145,7 +5226,8 @@ int fecgpu_rlc_span_decode(void *src, const void *rep, uint64_t nspans, uint32_t
   hipStream_t s = (hipStream_t)stream;
   if ((rc = span_plan_launch(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace, s)))
     return rc;
-  return decode_apply_impl(src, rep, src, nspans, k, r, symbol_size, status, recovered, workspace, workspace_bytes, s);
+  return decode_apply_impl(src, rep, src, nspans, k, r, symbol_size, status, recovered, workspace, workspace_bytes, s,
+                           0, true);
 }
 
 // The same with rows by address and a length each: the span plan, then the fused row forms' data pass.
@@ -5170,7 +5252,7 @@ int fecgpu_rlc_span_decode_rows_fused(const uint64_t *src_rows, const uint32_t *
   if ((rc = span_plan_launch(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace, s)))
     return rc;
   return decode_rows_fused_pass(src_rows, src_len, rep_rows, rep_len, blk_len, nspans, k, r, symbol_size, status,
-                                recovered, (uint8_t *)workspace, s);
+                                recovered, (uint8_t *)workspace, s, true);
 }
 
 // host_path.hip: decode with the recovered rows to dst (library-internal); full != 0: full-rank mode

@@ -9,9 +9,15 @@ many whole windows as 128 columns and 128 repair slots hold, L 1200, independent
            (fecgpu_rlc_decode_rows_full, in the parent commit): no symbol is copied into per-window blocks,
            which favours this variant.  Its input masks are those of the received symbols (no window sees
            what another recovered).
-Per shape: the span plan kernel alone, both variants' totals (median, min-max over the repeats), symbols
-recovered and microseconds per recovered symbol.
-usage: python tools/span_decode_cost.py [--repeats N] [--loss P] [--small]"""
+  rows     fecgpu_rlc_span_decode_rows_fused on the same buffers, every row by address with its length (the
+           form the batching adapter's span jobs use)
+The span and rows variants run with knob span_compact at 0 and at 1 (the compacted data pass), all in the same
+interleaved loop.  The packed variant's 16-unknown tiles take the LDS-ring kernel, which the knob does not
+reach; the row form never takes the ring.
+Per shape and loss: the span plan kernel alone, every variant's total (median, min-max over the repeats),
+symbols recovered, microseconds per recovered symbol, and the share of rows the compacted data pass lists
+(from the plan records: per tile of 16 unknowns, the input slots with a non-zero coefficient, over K).
+usage: python tools/span_decode_cost.py [--repeats N] [--loss P ...] [--small]"""
 import argparse
 import os
 import statistics
@@ -24,7 +30,7 @@ from pquic_amd import BLOCK_RECOVERED, Engine  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--repeats", type=int, default=30)
-ap.add_argument("--loss", type=float, default=0.03)
+ap.add_argument("--loss", type=float, nargs="+", default=[0.01, 0.03])
 ap.add_argument("--small", action="store_true", help="1/16 of the spans (a quick look, not the committed figures)")
 args = ap.parse_args()
 
@@ -53,7 +59,30 @@ def med_range(xs):
     return f"{statistics.median(xs):10.1f} us  ({min(xs):.1f} - {max(xs):.1f})"
 
 
-def workload(k, r, step, L, nb):
+def pad16(x):
+    return (x + 15) & ~15
+
+
+def rows_listed(ws, nb, K, R, tile=16):
+    """Share of the K input slots the compacted setup lists, over every tile of `tile` unknowns of the plan
+    records in ws (the workspace layout of fec_engine.hip: header, unknowns, selection, slots, flags, D)."""
+    em = min(K, R)
+    off_d = 16 + 3 * pad16(em) + pad16(K)
+    stride = off_d + pad16(em * K) + pad16(em * em)
+    rec = ws[:nb * stride].view(nb, stride)
+    ok = rec[:, 0] == BLOCK_RECOVERED
+    e = torch.where(ok, rec[:, 1], torch.zeros_like(rec[:, 1])).to(torch.int64)
+    listed = tiles = 0
+    for r0 in range(0, em, tile):
+        n = min(tile, em - r0)
+        d = rec[:, off_d + r0 * K: off_d + (r0 + n) * K].view(nb, n, K) != 0
+        live = (torch.arange(r0, r0 + n, device=dev).unsqueeze(0) < e.unsqueeze(1)).unsqueeze(2)
+        listed += int((d & live).any(1).sum())
+        tiles += int((e > r0).sum())
+    return listed / max(tiles * K, 1), tiles
+
+
+def workload(k, r, step, L, nb, loss):
     W = min((128 - k) // step + 1, 128 // r)
     K, R = k + (W - 1) * step, W * r
     src = torch.empty((nb, K, L), dtype=torch.uint8, device=dev)
@@ -66,8 +95,8 @@ def workload(k, r, step, L, nb):
         rep[:, w * r:(w + 1) * r] = tmp
     del tmp
     g = torch.Generator(device="cpu").manual_seed(17)
-    present = (torch.rand((nb, K), generator=g) >= args.loss).to(dev)
-    rpresent = (torch.rand((nb, R), generator=g) >= args.loss).to(dev)
+    present = (torch.rand((nb, K), generator=g) >= loss).to(dev)
+    rpresent = (torch.rand((nb, R), generator=g) >= loss).to(dev)
     sp, rp = masks(present), masks(rpresent)
     seed = torch.arange(r, dtype=torch.int32, device=dev).repeat(W).repeat(nb, 1).contiguous()
     off = (torch.arange(W, device=dev) * step).repeat_interleave(r).to(torch.uint8).repeat(nb, 1).contiguous()
@@ -94,7 +123,28 @@ def workload(k, r, step, L, nb):
     wst = torch.empty(nw, dtype=torch.uint8, device=dev)
     wrec = torch.empty((nw, 2), dtype=torch.int64, device=dev)
 
-    def span(ev=None):
+    # row form: the span buffers' rows by address, every length L; its own copy of the received rows, since
+    # it decodes in place
+    rwork = work.clone()
+    f_srow = (rwork.data_ptr() + torch.arange(nb * K, device=dev) * L).contiguous()
+    f_len = torch.full((nb * K,), L, dtype=torch.int32, device=dev)
+    f_rlen = torch.full((nb * R,), L, dtype=torch.int32, device=dev)
+    f_blen = torch.full((nb,), L, dtype=torch.int32, device=dev)
+    fws = eng.alloc_workspace(nb, K, R)
+    fst = torch.empty(nb, dtype=torch.uint8, device=dev)
+    frec = torch.empty((nb, 2), dtype=torch.int64, device=dev)
+
+    def rows(compact, ev=None):
+        eng.set_knob("span_compact", compact)
+        if ev:
+            ev[0].record()
+        eng.rlc_span_decode_rows_fused(f_srow, f_len, rrow, f_rlen, f_blen, seed, off, nss, sp, rp, fst, frec, nb, K, R,
+                                       L, workspace=fws)
+        if ev:
+            ev[2].record()
+
+    def span(compact=1, ev=None):
+        eng.set_knob("span_compact", compact)
         if ev:
             ev[0].record()
         eng.rlc_span_decode_plan(seed, off, nss, sp, rp, K, R, nb, ws)
@@ -112,17 +162,27 @@ def workload(k, r, step, L, nb):
             ev[2].record()
 
     for _ in range(2):
-        span()
+        for c in (0, 1):
+            span(c)
+            rows(c)
+            rwork.copy_(work)
         windows()
         wwork.copy_(work)
     torch.cuda.synchronize()
-    t = {"plan": [], "span": [], "windows": []}
-    for _ in range(args.repeats):  # interleaved: drift hits both variants alike
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        span(ev)
-        ev[2].synchronize()
-        t["plan"].append(ev[0].elapsed_time(ev[1]) * 1e3)
-        t["span"].append(ev[0].elapsed_time(ev[2]) * 1e3)
+    t = {"plan": [], "span0": [], "span": [], "rows0": [], "rows1": [], "windows": []}
+    for _ in range(args.repeats):  # interleaved: drift hits every variant alike
+        for c in (0, 1):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            span(c, ev)
+            ev[2].synchronize()
+            if c:
+                t["plan"].append(ev[0].elapsed_time(ev[1]) * 1e3)
+            t["span" if c else "span0"].append(ev[0].elapsed_time(ev[2]) * 1e3)
+            rwork.copy_(work)  # the row form decodes in place: every repeat starts from the received rows
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            rows(c, ev)
+            ev[2].synchronize()
+            t[f"rows{c}"].append(ev[0].elapsed_time(ev[2]) * 1e3)
         wwork.copy_(work)  # the window variant decodes in place: every repeat starts from the received rows
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         windows(ev)
@@ -131,6 +191,11 @@ def workload(k, r, step, L, nb):
     # what each variant recovered; the span variant's rows against the sources
     det = bits(rec, K) & ~present
     n_span = int(det.sum())
+    share, tiles = rows_listed(ws, nb, K, R)
+    assert bool((fst == st).all()) and bool((frec == rec).all()), "row form: status / recovered differ"
+    for c0 in range(0, nb, 2048):
+        same = (rwork[c0:c0 + 2048] == src[c0:c0 + 2048]).all(2)
+        assert bool((same == (present[c0:c0 + 2048] | det[c0:c0 + 2048])).all()), "row form rows differ"
     eng.rlc_span_decode(work, rep, seed, off, nss, sp, rp, st, rec, K, R, L, nspans=nb, workspace=ws)
     torch.cuda.synchronize()
     for c0 in range(0, nb, 2048):
@@ -143,17 +208,22 @@ def workload(k, r, step, L, nb):
     wdet &= ~present
     n_win = int(wdet.sum())
     assert bool((wdet & ~det).sum() == 0), "a window recovered what the span decode did not"
-    print(f"k{k} r{r} step {step}: spans of {W} windows, K {K}, R {R}, L {L}, {nb} spans, loss {args.loss:g}, "
+    print(f"k{k} r{r} step {step}: spans of {W} windows, K {K}, R {R}, L {L}, {nb} spans, loss {loss:g}, "
           f"{args.repeats} interleaved repeats")
     print(f"  lost symbols {lost}; recovered: windows {n_win} ({100 * n_win / lost:.2f} %), span {n_span} "
           f"({100 * n_span / lost:.2f} %); spans recovered {int((st == BLOCK_RECOVERED).sum())}")
     print(f"  span plan kernel     {med_range(t['plan'])}")
-    print(f"  span plan + apply    {med_range(t['span'])}   {statistics.median(t['span']) / max(n_span, 1):.4f} us per recovered symbol")
+    print(f"  rows the compacted pass lists: {share:.3f} of K per tile of 16 unknowns ({tiles} tiles)")
+    print(f"  span plan + apply, span_compact 0   {med_range(t['span0'])}")
+    print(f"  span plan + apply, span_compact 1   {med_range(t['span'])}   {statistics.median(t['span']) / max(n_span, 1):.4f} us per recovered symbol")
+    print(f"  row form, span_compact 0            {med_range(t['rows0'])}")
+    print(f"  row form, span_compact 1            {med_range(t['rows1'])}   {statistics.median(t['rows1']) / max(n_span, 1):.4f} us per recovered symbol")
     print(f"  windows ({nw} blocks) {med_range(t['windows'])}   {statistics.median(t['windows']) / max(n_win, 1):.4f} us per recovered symbol",
           flush=True)
 
 
 nspans = (1 << 16) // (16 if args.small else 1)
-for shape in ((30, 1, 5), (30, 5, 25), (32, 8, 8)):
-    workload(*shape, 1200, nspans)
-    torch.cuda.empty_cache()
+for loss in args.loss:
+    for shape in ((30, 1, 5), (30, 5, 25), (32, 8, 8)):
+        workload(*shape, 1200, nspans, loss)
+        torch.cuda.empty_cache()
