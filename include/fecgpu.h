@@ -24,7 +24,10 @@
  * (fbn << 8) | i, exactly as the reference (fec.h:44-75).
  *
  * `stream` is a hipStream_t (NULL = the null stream).  Every call is asynchronous and
- * graph-capturable: no allocation, no synchronisation inside.
+ * graph-capturable: no allocation, no synchronisation inside.  Call fecgpu_init(device) before capturing: its
+ * once-per-device check (one allocation, one synchronisation) otherwise runs inside the first launch.  The one
+ * other first-use step sits behind an experiment knob: with plan = 2 forced, shapes whose lane plan needs more
+ * than 64 KiB of LDS raise that kernel's limit (hipFuncSetAttribute) at their first plan call; make it eagerly.
  */
 #ifndef PQUIC_FECGPU_H
 #define PQUIC_FECGPU_H
