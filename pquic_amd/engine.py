@@ -74,6 +74,8 @@ def load_library(path: str = LIB_PATH, private: bool = False):
     L.fecgpu_rlc_decode_host_seeded.argtypes = [v, v, v, u64, u32, u32, u32, v, v, v, v, v]
     L.fecgpu_xor_encode_host.argtypes = [v, v, v, u64, u32, u32]
     L.fecgpu_xor_decode_host.argtypes = [v, v, v, u64, u32, u32, v, v, v, v]
+    if hasattr(L, "fecgpu_rlc_window_encode_host"):  # an older build (A/B baselines) may lack it
+        L.fecgpu_rlc_window_encode_host.argtypes = [v, v, u64, v, u64, u32, u32, u32, v]
     L.fecgpu_host_register.argtypes = [v, sz]
     L.fecgpu_host_unregister.argtypes = [v]
     L.fecgpu_host_device_address.argtypes = [v, sz, C.POINTER(u64)]
@@ -600,6 +602,11 @@ class HostPath:
     def rlc_encode(self, src, rep, nblocks, k, r, L, fbn_base=0):
         self._chk(self.lib.fecgpu_rlc_encode_host(self.ctx, _addr(src), _addr(rep), nblocks, k, r, L, fbn_base,
                                                   None), "fecgpu_rlc_encode_host")
+
+    def rlc_window_encode(self, symbols, nrows, wrow, rep, nwindows, k, r, L):
+        """fecgpu_rlc_window_encode_host: window w = rows wrow[w] .. wrow[w] + k of the stream (wrow: host u32)."""
+        self._chk(self.lib.fecgpu_rlc_window_encode_host(self.ctx, _addr(symbols), nrows, _addr(wrow), nwindows, k, r,
+                                                         L, _addr(rep)), "fecgpu_rlc_window_encode_host")
 
     def rlc_decode(self, src, rep, sp, rp, status, rec, nblocks, k, r, L, fbn_base=0):
         self._chk(self.lib.fecgpu_rlc_decode_host(self.ctx, _addr(src), _addr(rep), nblocks, k, r, L, fbn_base,
