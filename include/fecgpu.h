@@ -420,13 +420,22 @@ int fecgpu_rlc_span_decode(void *src, const void *rep, uint64_t nspans, uint32_t
  * repair shorter than it counts as zero-padded, which is exact (every source of that window is at most as
  * long).  Every determined source receives exactly blk_len[b] bytes at its own row; no other row is
  * written, nothing is written past blk_len[b], and a repair the plan does not select is never
- * dereferenced. */
+ * dereferenced.
+ * One launch for a few spans: with nspans <= 64, knob "plan" at 0 (as for fecgpu_rlc_decode_full: knob plan
+ * != 0 forces the separate launches) and a shape whose plan scratch and plan record fit 64 KiB of LDS
+ * together (K 128 with R 32 does, about 21 KiB; K = R = 128 does not), one kernel plans each span and runs
+ * its data pass in tiles of at most 8 unknowns, the record never leaving LDS.  Arguments, checks, outputs
+ * and the workspace requirement are the same; the workspace is not written on that path.  Every other call
+ * runs the plan kernel, a data-pass launch per tile of unknowns and the finalize kernel.  Same bytes either
+ * way.  fecgpu_rlc_span_decode and the plan / apply pair always keep their launches. */
 int fecgpu_rlc_span_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
                                       const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nspans, uint32_t K,
                                       uint32_t R, uint32_t symbol_size, const uint32_t *rep_seed,
                                       const uint8_t *rep_off, const uint8_t *rep_nss, const uint64_t *src_present,
                                       const uint64_t *rep_present, uint8_t *status, uint64_t *recovered,
                                       void *workspace, size_t workspace_bytes, void *stream);
+/* The fecgpu_rlc_span_decode_rows_fused calls of this process that ran as one launch (the rule above). */
+uint64_t fecgpu_rlc_span_one_launch_calls(void);
 /* From a receiver's window to a span (host only, no device): first_id[i] and nss[i] are the window start
  * (the repair's fec_scheme_specific) and length of received repair i, m of them.  Differences are taken
  * modulo 2^32 from first_id[0], so ids may wrap.  *base_id is the span's first symbol id, *K its width,

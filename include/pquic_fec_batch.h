@@ -143,14 +143,7 @@ int pquic_fec_batch_recover(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_f
  * (its fec_scheme_specific field, window_framework_receiver.h:60-86) and is seeded by its own FPID
  * (rep[i]->fpid.f.source_fpid.raw), as fec_recover seeds every equation.  Every missing column the repairs
  * determine is recovered, through neighbouring windows where no window alone would do. */
-typedef struct {
-    uint32_t base_id;                    /* stream id of column 0 (ids modulo 2^32) */
-    uint32_t K, R;                       /* 1..128 columns, 1..128 received repairs */
-    pquic_source_symbol_t *const *src;   /* [K], NULL where the symbol is missing */
-    pquic_repair_symbol_t *const *rep;   /* [R], none NULL; seed = its FPID as in fec_recover */
-    const uint32_t *first_id;            /* [R] window start of repair i (fec_scheme_specific) */
-    const uint8_t *nss;                  /* [R] window length of repair i */
-} pquic_fec_span_t;
+/* (pquic_fec_span_t: pquic_fec_protoops.h, which the blocking call pquic_fec_rlc_recover_span shares) */
 /* Called once per accepted span, on the caller's thread.  recovered[c] is the symbol recovered for column c or
  * NULL; the array is the batcher's and valid during the call, the symbols are the caller's from then on. */
 typedef void (*pquic_fec_span_done_fn)(void *user, const pquic_fec_span_t *sp,

@@ -147,6 +147,44 @@ int pquic_fec_unregister_heap(void *base);
  * staging row, out[2] calls the block service's worker served, out[3] calls that took a launch form. */
 void pquic_fec_hook_rows_stats(uint64_t out[4]);
 
+/* A span of the sliding-window receiver's stream, for span recovery (opt-in, beyond the reference): the joint
+ * decode of the framework's overlapping windows (fecgpu_rlc_span_decode, fecgpu.h).  K consecutive symbols of
+ * one connection's stream -- ids base_id .. base_id + K - 1 modulo 2^32 -- with the received ones in src[] and
+ * R received repair symbols, each with the window it protects: repair i covers the nss[i] symbols from stream
+ * id first_id[i] and is seeded by its own FPID, as fec_recover seeds every equation. */
+typedef struct {
+    uint32_t base_id;                    /* stream id of column 0 (ids modulo 2^32) */
+    uint32_t K, R;                       /* 1..128 columns, 1..128 received repairs */
+    pquic_source_symbol_t *const *src;   /* [K], NULL where the symbol is missing */
+    pquic_repair_symbol_t *const *rep;   /* [R], none NULL; seed = its FPID as in fec_recover */
+    const uint32_t *first_id;            /* [R] window start of repair i (fec_scheme_specific) */
+    const uint8_t *nss;                  /* [R] window length of repair i */
+} pquic_fec_span_t;
+/* Span recovery, blocking (one span per call, serialised like the operations above): every missing column
+ * the span's repairs determine is recovered, through neighbouring windows where no window alone would do.
+ * The semantics are those of a batcher span completion (pquic_fec_batch_recover_span, pquic_fec_batch.h), so
+ * one span gives the same symbols through either path.
+ * Returns PQUIC_FEC_ERR_UNBOUND with *nrecovered = 0 and nothing allocated: before pquic_fec_bind_host, for a
+ * NULL argument or table entry, K or R outside 1..128, a repair with nss == 0 or a window that leaves [0, K)
+ * (column offsets are first_id[i] - base_id modulo 2^32), and against an engine library without
+ * fecgpu_rlc_span_decode_rows_fused_host.  (No symbol is longer than 32767 bytes: data_length has 15 bits.)  A span with no missing column returns 0
+ * with nothing recovered.
+ * Otherwise one source symbol is allocated through the bound allocator for every missing column:
+ * data_length = the span's length (the largest data_length among its repairs; a received source counts for
+ * at most that many bytes), fpid.raw = base_id + column.  A symbol whose data is 4-byte aligned and lies in
+ * page-locked memory the engine knows (pquic_fec_register_heap, a batcher's arena) is read or written where
+ * it lies, for its own length; any other goes through a staging row -- whatever pquic_fec_set_hooks_in_place
+ * says, which keeps governing generate and recover only; pquic_fec_hook_rows_stats counts these rows too.
+ * The span is decoded by one fecgpu_rlc_span_decode_rows_fused_host call (one kernel launch for every shape
+ * whose plan fits LDS, fecgpu.h).  On success the return is 0, recovered[c] is the symbol of every column c of
+ * the engine's recovered[] mask (a determined source that is all zero is not handed over) and NULL elsewhere,
+ * *nrecovered their number; every other pre-allocation has been freed first, in column order; the symbols
+ * are the caller's.  A span with losses and repairs that determines nothing returns 0 with *nrecovered = 0
+ * and counts in pquic_fec_singular_blocks().  recover_calls and recovered_symbols count as for recover.  On
+ * an engine error every pre-allocation is freed, errors counts and PQUIC_FEC_ERR_UNBOUND is returned. */
+protoop_arg_t pquic_fec_rlc_recover_span(picoquic_cnx_t *cnx, const pquic_fec_span_t *sp,
+                                         pquic_source_symbol_t **recovered /* [sp->K] */, uint32_t *nrecovered);
+
 /* packet_payload_to_source_symbol (protoops/packet_payload_to_source_symbol.c:6-36, manifest
  * fec_core.plugin:20): inputs [0] payload bytes, [1] symbol buffer, [2] payload length,
  * [3] packet number; returns the symbol length, PQUIC_ERROR_MEMORY for a NULL buffer, or

@@ -196,8 +196,8 @@ struct WsLayout {
 
 __host__ __device__ constexpr static inline uint32_t pad16(uint32_t x) { return (x + 15u) & ~15u; }
 
-__host__ __device__ static inline WsLayout ws_layout(uint32_t k, uint32_t r) {
-  WsLayout w;
+__host__ __device__ constexpr static inline WsLayout ws_layout(uint32_t k, uint32_t r) {
+  WsLayout w{};
   w.em = k < r ? k : r;
   uint32_t o = 16;  // header: status, e
   w.off_unk = o;  o += pad16(w.em);
@@ -2005,7 +2005,7 @@ struct RecoverLds {
                      // need no registers across it)
   uint8_t *unk;      // [G][16] unknown -> source index (fused finalize)
   uint32_t *depm;    // [G][16] unknowns row u still references after elimination (fused finalize)
-  __host__ __device__ static size_t bytes(int G, int k) {
+  __host__ __device__ static constexpr size_t bytes(int G, int k) {
     return (size_t)G * ((size_t)k * (CSB + 8) + kDecRec + 16 + 64) + 256;
   }
   __device__ RecoverLds(uint8_t *l, int G, int k) {
@@ -2439,6 +2439,73 @@ __global__ __launch_bounds__(64) void k_rlc_decode_small(uint8_t *__restrict__ s
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     FEC_STAMP_AT(4);
+  }
+}
+
+// Span decode of a few spans in ONE launch (a receiver that decodes one span per call): the span's workgroup
+// runs the span plan, keeps the record in LDS as k_rlc_decode_small does, and runs the length-aware data pass
+// on the row tables from it.  The host cannot know e, the number of determined unknowns, so the tile is at
+// most kSpanSmallTile unknowns wide and the kernel reads e from the record: e <= RT is one pass with the
+// zero/undetermined rule fused; more takes a pass per RT unknowns with the non-zero flags OR-ed into the LDS
+// record, then the rule from that record.  One span per workgroup: all of this is wave-uniform.
+// LDS: the scratch both phases alias (the plan's; the data pass' tables with the compacted setup's lists at
+// cmp_off behind them) and, past it at rec_off, the record.  On the looping path the data pass ORs the non-zero
+// flags in through the 64-bit address it keeps per block (kDecRecNzPtr = ws + b * stride + off_nz + r0): here
+// that is a generic address that points into LDS, on purpose -- k_rlc_decode_small, always fused, never
+// stores through it -- and the barrier after each pass orders those stores before lane 0 reads the record.
+constexpr int kSpanSmallTile = 8;
+__host__ __device__ constexpr static inline int span_small_tile(uint32_t k, uint32_t r) {
+  const uint32_t em = k < r ? k : r;
+  return em <= 1 ? 1 : em <= 2 ? 2 : em <= 4 ? 4 : kSpanSmallTile;  // min(decode_tile(em), kSpanSmallTile)
+}
+__host__ __device__ constexpr static inline uint32_t span_small_cmp_off(uint32_t k, int rt) {
+  return pad16((uint32_t)(rt >= 8 ? RecoverLds<8>::bytes(1, (int)k) : RecoverLds<4>::bytes(1, (int)k)));
+}
+static_assert(RecoverLds<1>::CSB == RecoverLds<4>::CSB && RecoverLds<2>::CSB == RecoverLds<4>::CSB,
+              "tiles of 1, 2 and 4 unknowns share a coefficient row size");
+static_assert(kSpanSmallTile == 8, "span_small_cmp_off knows the tiles up to 8");
+__host__ __device__ constexpr static inline uint32_t span_small_rec_off(uint32_t k, uint32_t r, int rt) {
+  const size_t pl = plan_span_lds_bytes(k, r), rl = (size_t)span_small_cmp_off(k, rt) + 80 + k;
+  return pad16((uint32_t)(pl > rl ? pl : rl));
+}
+__host__ __device__ constexpr static inline size_t span_small_lds_bytes(uint32_t k, uint32_t r) {
+  return (size_t)span_small_rec_off(k, r, span_small_tile(k, r)) + pad16(ws_layout(k, r).stride);
+}
+static_assert(span_small_lds_bytes(128, 32) <= 65536, "K 128, R 32 decodes in one launch (21 120 B)");
+static_assert(span_small_lds_bytes(128, 128) > 65536, "K = R = 128 keeps the separate launches (85 936 B)");
+
+template <int RT, int VEC>
+__global__ __launch_bounds__(64) void k_rlc_span_decode_small(
+    uint8_t *__restrict__ src_rows, const uint8_t *__restrict__ rep_rows, const uint32_t *__restrict__ src_len,
+    const uint32_t *__restrict__ rep_len, const uint32_t *__restrict__ blk_len, uint64_t nspans, int k, int r, int L,
+    int nchunks, int chunk_bytes, const uint32_t *seeds, const uint8_t *roff, const uint8_t *rnss, const uint64_t *sp,
+    const uint64_t *rp, uint32_t cmp_off, uint32_t rec_off, uint8_t *status, uint64_t *recovered) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  const WsLayout WL = ws_layout((uint32_t)k, (uint32_t)r);
+  for (uint64_t b = blockIdx.x; b < nspans; b += gridDim.x) {
+    uint8_t *h = lds + rec_off;  // the span's record; both phases find it at wsx + b * stride
+    uint8_t *wsx = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(h) - b * (uint64_t)WL.stride);
+    __syncthreads();
+    plan_load_tables(lds);
+    plan_span_wave_block(b, k, r, seeds, roff, rnss, sp, rp, wsx, lds);
+    __syncthreads();
+    const int e = __builtin_amdgcn_readfirstlane(h[0] == FECGPU_BLOCK_RECOVERED ? (int)h[1] : 0);
+    const bool fused = e <= RT;  // NOTHING and SINGULAR too: the pass writes their status and touches no row
+    int r0 = 0;
+    do {
+      recover_bs_group<RT, VEC, true>(b, nspans, 1, src_rows, rep_rows, nspans, k, r, L, nchunks, chunk_bytes, wsx, r0,
+                                      1, fused ? status : nullptr, fused ? recovered : nullptr, 0, nullptr, lds,
+                                      nullptr, -1, src_len, rep_len, blk_len, cmp_off ? lds + cmp_off : nullptr);
+      __syncthreads();
+      r0 += RT;
+    } while (r0 < e);
+    if (!fused && threadIdx.x == 0) {  // rlc_fec_scheme_gf256.c:98-101, 218-236 from the record's flags
+      uint64_t m0, m1;
+      rlc_finalize_block(h, WL, h + WL.off_nz, m0, m1);
+      status[b] = (uint8_t)FECGPU_BLOCK_RECOVERED;
+      recovered[2 * b] = m0;
+      recovered[2 * b + 1] = m1;
+    }
   }
 }
 
@@ -5230,7 +5297,30 @@ int fecgpu_rlc_span_decode(void *src, const void *rep, uint64_t nspans, uint32_t
                            0, true);
 }
 
-// The same with rows by address and a length each: the span plan, then the fused row forms' data pass.
+extern "C++" {
+template <int RT, int VEC>
+static void launch_span_decode_small(const uint64_t *src_rows, const uint64_t *rep_rows, const uint32_t *src_len,
+                                     const uint32_t *rep_len, const uint32_t *blk_len, uint64_t ns, uint32_t k,
+                                     uint32_t r, int L, const BsCfg &c, const uint32_t *seeds, const uint8_t *roff,
+                                     const uint8_t *rnss, const uint64_t *sp, const uint64_t *rp, uint8_t *status,
+                                     uint64_t *recovered, hipStream_t s) {
+  static_assert(RT <= kSpanSmallTile, "span_small_lds_bytes sizes the LDS for tiles up to kSpanSmallTile");
+  const uint32_t cmp_off = knob(K_SPAN_COMPACT) ? span_small_cmp_off(k, RT) : 0;
+  hipLaunchKernelGGL((k_rlc_span_decode_small<RT, VEC>), dim3((uint32_t)ns), dim3(64), span_small_lds_bytes(k, r), s,
+                     (uint8_t *)src_rows, (const uint8_t *)rep_rows, src_len, rep_len, blk_len, ns, (int)k, (int)r, L,
+                     c.nchunks, c.chunk_bytes, seeds, roff, rnss, sp, rp, cmp_off, span_small_rec_off(k, r, RT), status,
+                     recovered);
+}
+}  // extern "C++"
+
+// Up to this many spans a span decode on rows is one launch (k_rlc_span_decode_small), as a decode of up to
+// kDecodeSmallMaxBlocks blocks is.
+constexpr uint64_t kSpanSmallMaxSpans = kDecodeSmallMaxBlocks;
+static std::atomic<uint64_t> g_span_one_launch{0};
+uint64_t fecgpu_rlc_span_one_launch_calls(void) { return g_span_one_launch.load(std::memory_order_relaxed); }
+
+// The same with rows by address and a length each: a few spans in one launch (knob plan != 0 forces the
+// separate launches), else the span plan, then the fused row forms' data pass.
 int fecgpu_rlc_span_decode_rows_fused(const uint64_t *src_rows, const uint32_t *src_len, const uint64_t *rep_rows,
                                       const uint32_t *rep_len, const uint32_t *blk_len, uint64_t nspans, uint32_t k,
                                       uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
@@ -5249,6 +5339,26 @@ int fecgpu_rlc_span_decode_rows_fused(const uint64_t *src_rows, const uint32_t *
   if (!status || !recovered) return set_err(FECGPU_ERR_INVALID, "%s", "span: NULL status / recovered");
   if ((uintptr_t)recovered % 8) return set_err(FECGPU_ERR_INVALID, "%s", "span: recovered must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
+  if (nspans <= kSpanSmallMaxSpans && knob(K_PLAN) == 0 && span_small_lds_bytes(k, r) <= 65536) {
+    if (int rc2 = bs_table_check()) return rc2;
+    count_decode(nspans);
+    const BsCfg cfg = pick_bs_cfg((int)symbol_size);
+#define FEC_SPAN_SMALL(RT, VEC)                                                                                     \
+  launch_span_decode_small<RT, VEC>(src_rows, rep_rows, src_len, rep_len, blk_len, nspans, k, r, (int)symbol_size, \
+                                    cfg, rep_seed, rep_off, rep_nss, src_present, rep_present, status, recovered, s)
+    switch (span_small_tile(k, r) * 100 + cfg.vec) {  // the workspace is not written on this path
+      case 116: FEC_SPAN_SMALL(1, 16); break;  case 108: FEC_SPAN_SMALL(1, 8); break;
+      case 104: FEC_SPAN_SMALL(1, 4); break;   case 216: FEC_SPAN_SMALL(2, 16); break;
+      case 208: FEC_SPAN_SMALL(2, 8); break;   case 204: FEC_SPAN_SMALL(2, 4); break;
+      case 416: FEC_SPAN_SMALL(4, 16); break;  case 408: FEC_SPAN_SMALL(4, 8); break;
+      case 404: FEC_SPAN_SMALL(4, 4); break;   case 816: FEC_SPAN_SMALL(8, 16); break;
+      case 808: FEC_SPAN_SMALL(8, 8); break;   default: FEC_SPAN_SMALL(8, 4); break;
+    }
+#undef FEC_SPAN_SMALL
+    HIPCHK(hipGetLastError());
+    g_span_one_launch.fetch_add(1, std::memory_order_relaxed);
+    return FECGPU_OK;
+  }
   if ((rc = span_plan_launch(nspans, k, r, rep_seed, rep_off, rep_nss, src_present, rep_present, workspace, s)))
     return rc;
   return decode_rows_fused_pass(src_rows, src_len, rep_rows, rep_len, blk_len, nspans, k, r, symbol_size, status,

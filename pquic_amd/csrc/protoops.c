@@ -55,6 +55,8 @@ static int g_recover_mode; /* 0 reference, 1 full rank (pquic_fec_set_recover_mo
 #pragma weak fecgpu_rlc_decode_rows_fused_host_full
 #pragma weak fecgpu_xor_encode_rows_host
 #pragma weak fecgpu_xor_decode_rows_host
+/* And span recovery: without the span decode on rows pquic_fec_rlc_recover_span refuses every span. */
+#pragma weak fecgpu_rlc_span_decode_rows_fused_host
 static int g_in_place;          /* pquic_fec_set_hooks_in_place, under g_mu */
 static uint64_t g_row_stats[4]; /* rows in place, rows staged, calls the worker served, calls launched; under g_mu */
 static fecgpu_host_ctx_t *g_ctx;
@@ -242,9 +244,11 @@ protoop_arg_t pquic_fec_xor_create_fec_schemes(picoquic_cnx_t *cnx) {
 /* The row tables of one block (under g_mu).  A symbol whose data is 4-byte aligned and lies in page-locked
  * memory the engine knows is entered by its own address; any other goes through its row of g_src / g_rep
  * (stride L), which are page-locked. */
+#define ROWS_MAX FECGPU_MAX_K /* a block's 100 symbols, a span's 128 columns and slots */
+_Static_assert(ROWS_MAX >= PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK && ROWS_MAX >= FECGPU_MAX_R, "row tables hold a span");
 typedef struct {
-    uint64_t src[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK], rep[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK];
-    uint32_t src_len[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK], rep_len[PQUIC_FEC_MAX_SYMBOLS_PER_BLOCK];
+    uint64_t src[ROWS_MAX], rep[ROWS_MAX];
+    uint32_t src_len[ROWS_MAX], rep_len[ROWS_MAX];
     uint64_t src_dev, rep_dev; /* device addresses of g_src / g_rep */
     uint32_t L;
 } rows_t;
@@ -524,6 +528,110 @@ static protoop_arg_t recover(picoquic_cnx_t *cnx, int xor_scheme) {
 
 protoop_arg_t pquic_fec_rlc_recover(picoquic_cnx_t *cnx) { return recover(cnx, 0); }
 protoop_arg_t pquic_fec_xor_recover(picoquic_cnx_t *cnx) { return recover(cnx, 1); }
+
+/* ------------------------------------------------------------------ span recovery */
+
+/* One span, blocking (pquic_fec_protoops.h): the checks and the pre-allocation of pquic_fec_batch_recover_span,
+ * the row tables of recover_in_place -- whatever g_in_place says -- one span decode on rows, and the completion
+ * of the batcher's span_finish. */
+protoop_arg_t pquic_fec_rlc_recover_span(picoquic_cnx_t *cnx, const pquic_fec_span_t *sp,
+                                         pquic_source_symbol_t **recovered, uint32_t *nrecovered) {
+    if (nrecovered) *nrecovered = 0;
+    if (!g_fec_bound || !sp || !recovered || !nrecovered) return PQUIC_FEC_ERR_UNBOUND;
+    if (fecgpu_rlc_span_decode_rows_fused_host == NULL) return PQUIC_FEC_ERR_UNBOUND;
+    if (sp->K < 1 || sp->K > FECGPU_MAX_K || sp->R < 1 || sp->R > FECGPU_MAX_R) return PQUIC_FEC_ERR_UNBOUND;
+    if (!sp->src || !sp->rep || !sp->first_id || !sp->nss) return PQUIC_FEC_ERR_UNBOUND;
+    const uint32_t K = sp->K, R = sp->R;
+    uint16_t maxl = 0; /* the span's length: the longest repair */
+    for (uint32_t i = 0; i < R; i++) {
+        const pquic_repair_symbol_t *rs = sp->rep[i];
+        const uint32_t off = sp->first_id[i] - sp->base_id; /* modulo 2^32 */
+        const uint32_t n = rs ? rs->data_length : 0; /* 15 bits: no symbol is longer than 32767 bytes */
+        if (!rs || (n && !rs->data)) return PQUIC_FEC_ERR_UNBOUND;
+        if (!sp->nss[i] || off >= K || sp->nss[i] > K - off) return PQUIC_FEC_ERR_UNBOUND;
+        if (n > maxl) maxl = (uint16_t)n;
+    }
+    uint32_t missing = 0;
+    for (uint32_t x = 0; x < K; x++) {
+        const pquic_source_symbol_t *ss = sp->src[x];
+        const uint32_t n = ss ? ss->data_length : 0;
+        if (!ss) missing++;
+        else if (n && !ss->data) return PQUIC_FEC_ERR_UNBOUND;
+    }
+    for (uint32_t x = 0; x < K; x++) recovered[x] = NULL;
+    if (!missing || !maxl) return 0; /* nothing to recover, or nothing to recover it from */
+    const uint32_t blk = maxl, L = fec_pad4(maxl);
+    pthread_mutex_lock(&g_mu);
+    FEC_STAT_ADD(recover_calls, 1);
+    rows_t *t = &g_rows;
+    fecgpu_host_ctx_t *c = rows_begin(t, (int)K, (int)R, L) ? NULL : ctx();
+    if (!c) {
+        FEC_STAT_ADD(errors, 1);
+        pthread_mutex_unlock(&g_mu);
+        return PQUIC_FEC_ERR_UNBOUND;
+    }
+    pquic_source_symbol_t **pre = recovered; /* the symbols allocated for the missing columns, numbered by stream id */
+    uint32_t seeds[ROWS_MAX];
+    uint8_t roff[ROWS_MAX], rnss[ROWS_MAX];
+    uint64_t spm[2] = {0, 0}, rpm[2] = {0, 0}, copy[2] = {0, 0}, rec[2] = {0, 0};
+    uint8_t st = FECGPU_BLOCK_NOTHING;
+    for (uint32_t x = 0; x < K; x++) {
+        const pquic_source_symbol_t *ss = sp->src[x];
+        uint8_t *row = g_src + (size_t)x * L;
+        const uint64_t row_dev = t->src_dev + (uint64_t)x * L;
+        if (ss) { /* a received source counts for at most the span's length */
+            t->src_len[x] = ss->data_length < maxl ? ss->data_length : maxl;
+            t->src[x] = row_input(ss->data, t->src_len[x], row, row_dev);
+            spm[x >> 6] |= 1ull << (x & 63);
+            continue;
+        }
+        /* a missing column: the row its recovered bytes go to -- the symbol allocated for it, or its staging row
+         * when that is not page-locked or was not allocated (copied out below) */
+        int in_place = 0;
+        pre[x] = fec_new_source(cnx, sp->base_id + x, maxl);
+        t->src_len[x] = 0;
+        t->src[x] = pre[x] ? row_address(pre[x]->data, blk, row_dev, &in_place) : row_dev;
+        if (!pre[x]) g_row_stats[1]++; /* its staging row, which row_address did not see */
+        if (!in_place) copy[x >> 6] |= 1ull << (x & 63);
+    }
+    for (uint32_t i = 0; i < R; i++) {
+        const pquic_repair_symbol_t *rs = sp->rep[i];
+        t->rep_len[i] = rs->data_length; /* at most the span's length, which is the largest of them */
+        t->rep[i] = row_input(rs->data, t->rep_len[i], g_rep + (size_t)i * L, t->rep_dev + (uint64_t)i * L);
+        rpm[i >> 6] |= 1ull << (i & 63);
+        seeds[i] = rs->fpid.f.source_fpid.raw; /* the repair's own FPID, as in fec_recover */
+        roff[i] = (uint8_t)(sp->first_id[i] - sp->base_id);
+        rnss[i] = sp->nss[i];
+    }
+    const int rc = fecgpu_rlc_span_decode_rows_fused_host(c, t->src, t->src_len, t->rep, t->rep_len, &blk, 1, K, R, L,
+                                                          seeds, roff, rnss, spm, rpm, &st, rec);
+    const int ok = !rc && st == FECGPU_BLOCK_RECOVERED;
+    if (rc) FEC_STAT_ADD(errors, 1);
+    else if (st == FECGPU_BLOCK_SINGULAR) __atomic_fetch_add(&g_fec_singular_blocks, 1, __ATOMIC_RELAXED);
+    if (!rc) row_call_done(0);
+    for (uint32_t x = 0; x < K; x++) { /* what the engine did not recover is freed first, in column order */
+        if ((ok && ((rec[x >> 6] >> (x & 63)) & 1)) || !pre[x]) continue;
+        g_fec_api.my_free(cnx, pre[x]->data);
+        g_fec_api.my_free(cnx, pre[x]);
+        pre[x] = NULL;
+    }
+    uint32_t nrec = 0;
+    for (uint32_t x = 0; ok && x < K; x++) {
+        if (!((rec[x >> 6] >> (x & 63)) & 1) || sp->src[x]) continue;
+        const uint8_t *row = g_src + (size_t)x * L;
+        if (!pre[x]) { /* the allocation before the call had failed: once more, skipped when that fails too */
+            if (!(pre[x] = fec_new_source(cnx, sp->base_id + x, maxl))) continue;
+            memcpy(pre[x]->data, row, maxl);
+        } else if ((copy[x >> 6] >> (x & 63)) & 1) {
+            memcpy(pre[x]->data, row, maxl);
+        }
+        nrec++;
+    }
+    if (nrec) FEC_STAT_ADD(recovered_symbols, nrec);
+    pthread_mutex_unlock(&g_mu);
+    *nrecovered = nrec;
+    return rc ? PQUIC_FEC_ERR_UNBOUND : 0;
+}
 
 /* ---- source-symbol capture ---- */
 static int skip_via_host(void *cnx, const uint8_t *bytes, size_t bytes_max, size_t *consumed, int *pure_ack) {

@@ -145,6 +145,9 @@ def load_library(path: str = LIB_PATH, private: bool = False):
         L.fecgpu_rlc_span_decode_rows_fused_host.argtypes = [v, v, v, v, v, v, u64, u32, u32, u32, v, v, v, v, v, v,
                                                              v]
         L.fecgpu_rlc_span_layout.argtypes = [v, v, u32, C.POINTER(u32), C.POINTER(u32), v]
+    if hasattr(L, "fecgpu_rlc_span_one_launch_calls"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks it
+        L.fecgpu_rlc_span_one_launch_calls.argtypes = []
+        L.fecgpu_rlc_span_one_launch_calls.restype = u64
     if hasattr(L, "fecgpu_rlc_window_encode_table"):
         L.fecgpu_rlc_window_encode_table.argtypes = [v, u64, v, u64, u32, u32, u32, v, v]
     if not private:
@@ -181,6 +184,12 @@ def span_layout(first_id, nss):
     return base.value, K.value, off[:len(ids)]
 
 
+def span_one_launch_calls(lib=None) -> int:
+    """fecgpu_rlc_span_one_launch_calls (host only): the span decode calls of this process that ran as one
+    launch (fecgpu_rlc_span_decode_rows_fused with at most 64 spans, knob plan 0 and a shape that fits LDS)."""
+    return int((lib or load_library()).fecgpu_rlc_span_one_launch_calls())
+
+
 class Engine:
     """Batched FEC engine on one device.  Mirrors fecgpu_* one to one."""
 
@@ -208,6 +217,10 @@ class Engine:
     def _check(self, rc, what):
         if rc != OK:
             raise FecGpuError(f"{what} failed ({rc}): {self.err()}")
+
+    def span_one_launch_calls(self) -> int:
+        """fecgpu_rlc_span_one_launch_calls of this engine's library."""
+        return span_one_launch_calls(self.lib)
 
     def get_knob(self, name: str) -> int:
         v = C.c_int(0)

@@ -1,6 +1,7 @@
 /*
  * tools/span_load.c -- host stand-in for a span receiver on the batching adapter
- * (pquic_fec_batch_recover_span, include/pquic_fec_batch.h), for the tests and the measurement.  Plays a
+ * (pquic_fec_batch_recover_span, include/pquic_fec_batch.h) and on the blocking call
+ * (pquic_fec_rlc_recover_span, include/pquic_fec_protoops.h), for the tests and the measurement.  Plays a
  * single-threaded picoquic receiver with several connections: every connection allocates from its own arena
  * (registered with the batcher or not), symbols are built from the caller's bytes, spans are submitted, and
  * every completion is recorded per ticket -- its place in the completion order, the value it returned and the
@@ -73,6 +74,12 @@ static uint64_t now_us(void) {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return (uint64_t)ts.tv_sec * 1000000u + (uint64_t)ts.tv_nsec / 1000u;
+}
+
+static uint64_t now_ns(void) {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (uint64_t)ts.tv_sec * 1000000000u + (uint64_t)ts.tv_nsec;
 }
 
 /* ---- the handle ---- */
@@ -248,20 +255,17 @@ static void on_done(void *user, const pquic_fec_span_t *sp, pquic_source_symbol_
     }
 }
 
-/* Submits a span of connection conn: src_ids[K] / rep_ids[R] are symbol ids (-1: NULL).  fault, for the
- * argument checks: 1 NULL src table, 2 NULL rep table, 3 NULL first_id, 4 NULL nss, 5 NULL done, 6 NULL span.
- * Returns the ticket (>= 0) when the call returned 0, -1 when it returned -1, -2 on a failure of its own. */
-long sl_submit(void *hv, int conn, uint32_t base_id, uint32_t K, uint32_t R, const long *src_ids, const long *rep_ids,
-               const uint32_t *first_id, const uint8_t *nss, uint64_t now, int fault) {
-    sl_t *h = hv;
+/* A ticket for a span of connection conn as the caller describes it (sl_submit), with room in the handle. */
+static ticket_t *ticket_new(sl_t *h, int conn, uint32_t base_id, uint32_t K, uint32_t R, const long *src_ids,
+                            const long *rep_ids, const uint32_t *first_id, const uint8_t *nss, int fault) {
     ticket_t *t = calloc(1, sizeof *t);
-    if (!t) return -2;
+    if (!t) return NULL;
     const uint32_t Ka = K ? K : 1, Ra = R ? R : 1;
     t->src = calloc(Ka > 256 ? 256 : Ka, sizeof *t->src);
     t->rep = calloc(Ra > 256 ? 256 : Ra, sizeof *t->rep);
     t->first_id = calloc(Ra > 256 ? 256 : Ra, sizeof *t->first_id);
     t->nss = calloc(Ra > 256 ? 256 : Ra, 1);
-    if (!t->src || !t->rep || !t->first_id || !t->nss) { ticket_free(t); return -2; }
+    if (!t->src || !t->rep || !t->first_id || !t->nss) { ticket_free(t); return NULL; }
     for (uint32_t x = 0; x < K && x < 256; x++) t->src[x] = src_ids[x] >= 0 ? h->syms[src_ids[x]] : NULL;
     for (uint32_t x = 0; x < R && x < 256; x++) {
         t->rep[x] = rep_ids[x] >= 0 ? h->syms[rep_ids[x]] : NULL;
@@ -275,10 +279,21 @@ long sl_submit(void *hv, int conn, uint32_t base_id, uint32_t K, uint32_t R, con
     if (h->ntk == h->tk_cap) {
         const long nc = h->tk_cap ? 2 * h->tk_cap : 256;
         ticket_t **nt = realloc(h->tk, sizeof *nt * (size_t)nc);
-        if (!nt) { ticket_free(t); return -2; }
+        if (!nt) { ticket_free(t); return NULL; }
         h->tk = nt;
         h->tk_cap = nc;
     }
+    return t;
+}
+
+/* Submits a span of connection conn: src_ids[K] / rep_ids[R] are symbol ids (-1: NULL).  fault, for the
+ * argument checks: 1 NULL src table, 2 NULL rep table, 3 NULL first_id, 4 NULL nss, 5 NULL done, 6 NULL span.
+ * Returns the ticket (>= 0) when the call returned 0, -1 when it returned -1, -2 on a failure of its own. */
+long sl_submit(void *hv, int conn, uint32_t base_id, uint32_t K, uint32_t R, const long *src_ids, const long *rep_ids,
+               const uint32_t *first_id, const uint8_t *nss, uint64_t now, int fault) {
+    sl_t *h = hv;
+    ticket_t *t = ticket_new(h, conn, base_id, K, R, src_ids, rep_ids, first_id, nss, fault);
+    if (!t) return -2;
     const int rc = pquic_fec_batch_recover_span(h->b, &h->cnx[conn], fault == 6 ? NULL : &t->sp, now,
                                                 fault == 5 ? NULL : on_done, t);
     if (rc) {
@@ -286,6 +301,31 @@ long sl_submit(void *hv, int conn, uint32_t base_id, uint32_t K, uint32_t R, con
         ticket_free(t);
         return called ? -3 : -1;  /* -3: refused, yet the callback ran */
     }
+    h->tk[h->ntk] = t;
+    return h->ntk++;
+}
+
+/* Runs a span of connection conn through the blocking call, pquic_fec_rlc_recover_span, and records what it
+ * handed over as a completion: sl_submit's arguments; fault 1-4 and 6 as there, 7 NULL recovered[], 8 NULL
+ * nrecovered.  Returns the ticket (>= 0) when the call returned 0, -1 when it returned PQUIC_FEC_ERR_UNBOUND
+ * with *nrecovered == 0 and recovered[] untouched or NULL, -3 for any other outcome, -2 on a failure of its own. */
+long sl_recover_span(void *hv, int conn, uint32_t base_id, uint32_t K, uint32_t R, const long *src_ids,
+                     const long *rep_ids, const uint32_t *first_id, const uint8_t *nss, int fault) {
+    sl_t *h = hv;
+    ticket_t *t = ticket_new(h, conn, base_id, K, R, src_ids, rep_ids, first_id, nss, fault);
+    if (!t) return -2;
+    pquic_source_symbol_t *poison = (pquic_source_symbol_t *)(uintptr_t)1, *rec[256];
+    for (int x = 0; x < 256; x++) rec[x] = poison;
+    uint32_t nrec = 0xdead;
+    const protoop_arg_t ret = pquic_fec_rlc_recover_span(&h->cnx[conn], fault == 6 ? NULL : &t->sp,
+                                                         fault == 7 ? NULL : rec, fault == 8 ? NULL : &nrec);
+    if (ret) {
+        int clean = ret == PQUIC_FEC_ERR_UNBOUND && (fault == 8 || nrec == 0);
+        for (int x = 0; x < 256; x++) clean = clean && (rec[x] == poison || rec[x] == NULL);
+        ticket_free(t);
+        return clean ? -1 : -3;
+    }
+    on_done(t, &t->sp, rec, nrec, ret);
     h->tk[h->ntk] = t;
     return h->ntk++;
 }
@@ -388,6 +428,100 @@ static void run_done(void *user, const pquic_fec_span_t *sp, pquic_source_symbol
 static int cmp_u64(const void *a, const void *b) {
     const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
     return (x > y) - (x < y);
+}
+
+/* The blocking call's latency: one connection (its arena registered or not) holds one span of nwin windows as
+ * sl_run builds them; ncalls times its losses are redrawn and, when a source is lost and a repair arrived, the
+ * received symbols go through pquic_fec_rlc_recover_span, timed from the call to its return; what it hands over
+ * is freed outside the timed part.  out: [0] p50 us, [1] p99 us, [2] min us, [3] lost source symbols, [4] recovered source symbols, [5] rows
+ * in place, [6] rows staged, [7] calls that returned an error, [8] calls timed.  Returns 0, or -1. */
+int sl_run_blocking(int device, int k, int r, int step, int nwin, int L, double p, long ncalls, int registered,
+                    unsigned seed, double *out) {
+    const int K = (nwin - 1) * step + k, R = nwin * r;
+    if (K < 1 || K > 128 || R < 1 || R > 128 || L < 4 || (L & 3) || L > BIG - HDR || ncalls < 1) return -1;
+    int rc = -1;
+    const uint8_t reg = registered ? 1 : 0;
+    sl_t *h = sl_open(device, 64, 100, (unsigned)L, 0, 1, (size_t)(K + R) * (BIG + SMALL) * 4 + (1u << 20), &reg);
+    if (!h) return -1;
+    picoquic_cnx_t *cnx = &h->cnx[0];
+    uint8_t *stream = fecgpu_host_alloc((size_t)K * L), *coded = fecgpu_host_alloc((size_t)R * L);
+    uint32_t wrow[128], first_id[128], all_first[128];
+    uint8_t nss[128];
+    pquic_source_symbol_t *all_src[128], *src[128], *rec[128];
+    pquic_repair_symbol_t *all_rep[128], *rep[128];
+    fecgpu_host_ctx_t *ctx = fecgpu_host_ctx_create(device, 2, 1u << 22);
+    uint64_t *lat = calloc((size_t)ncalls, sizeof *lat);
+    if (!stream || !coded || !ctx || !lat) goto out;
+    uint64_t g = seed * 2654435761u + 1;
+    for (size_t i = 0; i < (size_t)K * L; i += 8) {
+        const uint64_t v = rng_next(&g);
+        memcpy(stream + i, &v, (size_t)K * L - i < 8 ? (size_t)K * L - i : 8);
+    }
+    for (int w = 0; w < nwin; w++) wrow[w] = (uint32_t)(w * step);
+    if (fecgpu_rlc_window_encode_host(ctx, stream, (uint64_t)K, wrow, (uint64_t)nwin, (uint32_t)k, (uint32_t)r,
+                                      (uint32_t)L, coded) != FECGPU_OK)
+        goto out;
+    const uint32_t base = 0xfffffff0u;  /* the ids wrap inside the span */
+    for (int x = 0; x < K; x++) {
+        const long id = sl_source(h, 0, stream + (size_t)x * L, (unsigned)L, base + (uint32_t)x);
+        if (id < 0) goto out;
+        all_src[x] = h->syms[id];
+    }
+    for (int x = 0; x < R; x++) {
+        all_first[x] = base + (uint32_t)(x / r * step);
+        const long id = sl_repair(h, 0, coded + (size_t)x * L, (unsigned)L, (uint32_t)(x % r), all_first[x]);
+        if (id < 0) goto out;
+        all_rep[x] = h->syms[id];
+    }
+    memset(nss, k, sizeof nss);
+    const uint64_t thresh = p >= 1.0 ? UINT64_MAX : (uint64_t)(p * 18446744073709551615.0);
+    long nlat = 0, lost = 0, recovered = 0, errors = 0;
+    uint64_t rows0[4], rows1[4];
+    pquic_fec_hook_rows_stats(rows0);
+    for (long n = 0; n < ncalls; n++) {
+        uint32_t nr = 0, nrec = 0;
+        int gone_now = 0;
+        for (int x = 0; x < K; x++) {
+            const int gone = rng_next(&g) < thresh;
+            src[x] = gone ? NULL : all_src[x];
+            gone_now += gone;
+        }
+        if (!gone_now) continue;  /* nothing lost: the call would return before the engine */
+        lost += gone_now;
+        for (int x = 0; x < R; x++)
+            if (rng_next(&g) >= thresh) {
+                rep[nr] = all_rep[x];
+                first_id[nr++] = all_first[x];
+            }
+        if (!nr) continue;  /* no repair arrived: nothing to call */
+        const pquic_fec_span_t sp = {base, (uint32_t)K, nr, src, rep, first_id, nss};
+        const uint64_t t0 = now_ns();
+        const protoop_arg_t ret = pquic_fec_rlc_recover_span(cnx, &sp, rec, &nrec);
+        lat[nlat++] = now_ns() - t0;
+        if (ret) { errors++; continue; }
+        recovered += nrec;
+        for (int x = 0; x < K; x++)
+            if (rec[x]) { sl_free(cnx, rec[x]->data); sl_free(cnx, rec[x]); }
+    }
+    pquic_fec_hook_rows_stats(rows1);
+    qsort(lat, (size_t)nlat, sizeof *lat, cmp_u64);
+    out[0] = nlat ? (double)lat[nlat / 2] * 1e-3 : 0;
+    out[1] = nlat ? (double)lat[(long)((double)(nlat - 1) * 0.99)] * 1e-3 : 0;
+    out[2] = nlat ? (double)lat[0] * 1e-3 : 0;
+    out[3] = (double)lost;
+    out[4] = (double)recovered;
+    out[5] = (double)(rows1[0] - rows0[0]);
+    out[6] = (double)(rows1[1] - rows0[1]);
+    out[7] = (double)errors;
+    out[8] = (double)nlat;
+    rc = 0;
+out:
+    free(lat);
+    if (ctx) fecgpu_host_ctx_destroy(ctx);
+    fecgpu_host_free(stream);
+    fecgpu_host_free(coded);
+    sl_close(h);
+    return rc;
 }
 
 int sl_run(int device, int nconn, int k, int r, int step, int nwin, int L, double p, long nspans, int slots,
