@@ -562,6 +562,39 @@ int fecgpu_rlc_window_encode_rows_host(fecgpu_host_ctx_t *ctx, const uint64_t *r
                                        uint64_t nrows, const uint32_t *wrow, const uint64_t *rep_rows,
                                        const uint32_t *blk_len, uint64_t nwindows, uint32_t k, uint32_t r,
                                        uint32_t symbol_size);
+/* fecgpu_rlc_window_encode_rows_host for windows of their own length (the window sender protects whatever is
+ * in flight, 1 to 30 symbols, window_framework_sender.h:209-260): window w protects rows wrow[w] ..
+ * wrow[w] + wlen[w] - 1 with block number 0, wlen[w] in 1..kmax.  Repair row (w, i) receives exactly
+ * blk_len[w] bytes, those of an RLC encode of block 0 over these rows and r repairs, every row counting for
+ * min(row_len, blk_len[w]) bytes.  The coefficient of (position j, repair i) does not depend on the
+ * window's length, so the call sorts the windows into classes of one length
+ * (fecgpu_rlc_window_classes) and one launch per tile of 8 repairs codes them all, a 2 KiB chunk never
+ * holding two lengths.  Memory rules, alignment rules, clamps and the staging of the tables (perm and the
+ * class table go with them: in place when page-locked, else copied once) are those of
+ * fecgpu_rlc_window_encode_rows_host.  Before the context is looked at it checks NULL tables, the ranges
+ * of kmax, r and symbol_size, wlen[w] in 1..kmax ("wlen"), wrow[w] + wlen[w] <= nrows ("wrow"),
+ * row_len[x] <= symbol_size and blk_len[w] <= symbol_size, and returns FECGPU_ERR_INVALID with a message
+ * naming the rule, nothing written.  nwindows == 0 is FECGPU_OK without a launch.  When every wlen[w]
+ * equals kmax the call is fecgpu_rlc_window_encode_rows_host itself.  With knob window_sc 0, or
+ * (nrows + kmax) * width at 2 GiB or more, every window becomes a block of kmax rows through
+ * fecgpu_rlc_encode_rows_fused_host with block number 0, the positions past wlen[w] given as rows of
+ * length 0 and address 0 (never dereferenced): the same bytes. */
+int fecgpu_rlc_window_encode_rows_var_host(fecgpu_host_ctx_t *ctx, const uint64_t *rows, const uint32_t *row_len,
+                                           uint64_t nrows, const uint32_t *wrow, const uint8_t *wlen,
+                                           const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nwindows,
+                                           uint32_t kmax, uint32_t r, uint32_t symbol_size);
+/* The sort behind it (host only, no device): a stable counting sort of the windows by length.  perm[p] is
+ * the window at sorted position p (within a class the windows keep the caller's order, so neighbouring
+ * windows of one connection stay neighbours in time); the classes follow in order of length, class x
+ * holding cnt[x] windows of len[x] symbols from sorted position first[x], its windows x bytes space
+ * (cnt[x] * width, the width being symbol_size rounded up to 16) cut into 2 KiB chunks of its own from
+ * chunk cchunk[x] on.  cls holds four arrays of kmax entries, first[], cnt[], len[], cchunk[], in that
+ * order; entries past *nclasses are 0, their cchunk 2^32 - 1.  *nchunks = sum of ceil(cnt[x] * width /
+ * 2048).  FECGPU_ERR_INVALID, with a message naming the rule, for a NULL pointer, kmax outside 1..128, a
+ * symbol_size the encode would refuse, any wlen[w] outside 1..kmax, or 2^32 - 1 windows or chunks. */
+int fecgpu_rlc_window_classes(const uint8_t *wlen, uint64_t nwin, uint32_t kmax, uint32_t symbol_size,
+                              uint32_t *perm, uint32_t *cls /* [4 * kmax]: first, cnt, len, first chunk */,
+                              uint32_t *nclasses, uint64_t *nchunks);
 int fecgpu_xor_encode_host(fecgpu_host_ctx_t *ctx, const void *src, void *rep, uint64_t nblocks,
                            uint32_t k, uint32_t symbol_size);
 int fecgpu_xor_decode_host(fecgpu_host_ctx_t *ctx, void *src, const void *rep, uint64_t nblocks,

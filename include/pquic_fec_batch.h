@@ -69,14 +69,17 @@ typedef struct {
 } pquic_fec_batch_stats_t;
 
 /* NULL on failure (bad configuration, no device, out of pinned memory).
- * The adapter reads four environment variables, once per batcher, here (a value below the minimum
+ * The adapter reads five environment variables, once per batcher, here (a value below the minimum
  * counts as unset, one above the maximum as the maximum):
  *   PQUIC_FEC_BATCH_STAGERS   copy threads, 1..16; default half the CPUs of the process's share, at least 2
  *   PQUIC_FEC_BATCH_ENGINES   engine threads, each with its own host context and streams, 1..4; default 2
  *   PQUIC_FEC_BATCH_PREFETCH  blocks ahead a completion prefetches the symbols it hands over, 0..64
  *                             (0: off); default 8
  *   PQUIC_FEC_BATCH_FULL_RANK 0 or 1: the batcher starts in full-rank mode (pquic_fec_batch_set_full_rank);
- *                             default 0; ignored against an engine library without the full-rank entry points */
+ *                             default 0; ignored against an engine library without the full-rank entry points
+ *   PQUIC_FEC_BATCH_WINDOW_MIXED 0 or 1: the batcher starts with mixed window jobs
+ *                             (pquic_fec_batch_set_window_mixed); default 0; ignored against an engine library
+ *                             without fecgpu_rlc_window_encode_rows_var_host */
 pquic_fec_batcher_t *pquic_fec_batcher_create(const pquic_fec_batch_cfg_t *cfg);
 /* Drains (completing every queued block) and frees. */
 void pquic_fec_batcher_destroy(pquic_fec_batcher_t *b);
@@ -185,6 +188,23 @@ int pquic_fec_batch_recover_span(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, co
  * are not affected.  Call from the submitting thread.  Returns 0, or -1 while any block is queued or in
  * flight (drain first) and against an engine library without the three entry points. */
 int pquic_fec_batch_set_full_rank(pquic_fec_batcher_t *b, int on);
+
+/* Mixed window jobs (on != 0; 0, the default: a window queue per (k, r), nothing changes).  The window sender
+ * protects whatever is in flight, 1 to 30 symbols, a count that changes with every ACK and every send
+ * (window_protect_all_inflight_source_symbols.c:12-23), so under the default key its windows spread over up to
+ * 30 queues per r, each flushed on its deadline with a fraction of a batch, and a connection's run of stream
+ * rows ends at every change of length.  With mixed jobs pquic_fec_batch_generate_window queues a window under
+ * (kclass, r), kclass the smallest of 16, 32, 64 and 128 that holds total_source_symbols; the job records each
+ * window's length, matches and extends a connection's run with it (looking back at most kclass rows), and runs
+ * through fecgpu_rlc_window_encode_rows_var_host, always on rows by address: symbols and repairs in a
+ * registered heap where they lie, any other through the job's staging rows (there is no packed staged form; a
+ * job whose windows all have one length runs through fecgpu_rlc_window_encode_rows_host for that length).  r
+ * stays in the key: it differs from the controller's value only for windows shorter than n - k.  The 2 GiB
+ * test of pquic_fec_batch_generate_window (with kclass in it), buffer sizing, the provisioner, completion order
+ * (submission order), the FPIDs 0..r-1 and `done` exactly once are unchanged.  Call from the submitting
+ * thread.  Returns 0, or -1 while any block is queued or in flight (drain first) and against an engine library
+ * without fecgpu_rlc_window_encode_rows_var_host. */
+int pquic_fec_batch_set_window_mixed(pquic_fec_batcher_t *b, int on);
 
 /* Flushes every queue that is full or past its deadline at `now_us`, then runs `done` for
  * the blocks whose batch has finished: all of them, or at most cfg.poll_blocks.  Batches complete

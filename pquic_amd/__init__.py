@@ -8,8 +8,8 @@ library or a gfx950 device is missing, calls raise.
 """
 from .engine import Engine, FecGpuError, HostPath, load_library, LIB_PATH  # noqa: F401
 from .engine import BLOCK_RECOVERED, BLOCK_NOTHING, BLOCK_REF_UB, BLOCK_SINGULAR  # noqa: F401
-from .engine import span_layout, span_one_launch_calls  # noqa: F401
+from .engine import span_layout, span_one_launch_calls, window_classes  # noqa: F401
 
 __all__ = ["Engine", "FecGpuError", "HostPath", "load_library", "LIB_PATH", "span_layout",
-           "span_one_launch_calls",
+           "span_one_launch_calls", "window_classes",
            "BLOCK_RECOVERED", "BLOCK_NOTHING", "BLOCK_REF_UB", "BLOCK_SINGULAR"]

@@ -41,6 +41,13 @@
  * of copied, the device builds the stream from the rows, and a repair whose symbol lies in an arena is
  * written there by the kernel for the window's length; only symbols outside every arena go through the
  * staging rows, unpadded.
+ * Mixed window jobs (pquic_fec_batch_set_window_mixed, off by default): a real window sender's windows change
+ * length with every ACK and send, and under the key (op, k, r) they spread over up to 30 queues per r.  In
+ * mixed mode a window queues under (OP_WINDOW, kclass, r), kclass the smallest of 16, 32, 64, 128 that holds
+ * it, the job records each window's length, the run layout matches and extends a connection's run with the
+ * window's own length, and the job always runs on row tables (fecgpu_rlc_window_encode_rows_var_host, a
+ * weak reference as well): symbols and repairs in a registered arena go by address, any other through the
+ * job's staging rows by their device addresses.  There is no packed staged form for a mixed job.
  * Spans (pquic_fec_batch_recover_span): a span job is a recover job on rows by address whose "blocks" are
  * spans of one connection's stream, decoded jointly across their overlapping windows by
  * fecgpu_rlc_span_decode_rows_fused_host (weak as well: without it the call is refused).  Spans of any width
@@ -97,6 +104,10 @@ static int xor_rows_available(void) {
 /* And window jobs on rows where they lie: without it a window job's stream is copied into the staging rows. */
 #pragma weak fecgpu_rlc_window_encode_rows_host
 static int window_rows_available(void) { return fecgpu_rlc_window_encode_rows_host != NULL; }
+
+/* And windows of several lengths in one job (pquic_fec_batch_set_window_mixed): without it mixed mode is unavailable. */
+#pragma weak fecgpu_rlc_window_encode_rows_var_host
+static int window_mixed_available(void) { return fecgpu_rlc_window_encode_rows_var_host != NULL; }
 
 /* And span jobs: without it pquic_fec_batch_recover_span refuses every span. */
 #pragma weak fecgpu_rlc_span_decode_rows_fused_host
@@ -172,6 +183,9 @@ typedef struct job {
     size_t rowsym_cap;
     uint64_t nrows;                /* window: stream rows */
     int full;                      /* RLC recover: full-rank mode, the batcher's when the job was flushed */
+    int mixed;                     /* window: windows of several lengths (k is the key's class, wlen[] the lengths) */
+    uint8_t *wlen;                 /* mixed window: [cap] symbols of each window */
+    uint32_t wlo, whi;             /* mixed window: the shortest and the longest window queued */
     uint8_t *roff, *rnss;          /* span, pinned: [cap][r] column offset / length of each repair's window */
     size_t win_cap;
 } job_t;
@@ -193,6 +207,7 @@ struct pquic_fec_batcher {
     int inflight, stop, stagers_done;
     uint32_t pf;                   /* completion prefetch distance in blocks (prefetch_syms; 0: off) */
     int full_rank;                 /* caller thread: RLC recover jobs run in full-rank mode (set_full_rank) */
+    int window_mixed;              /* caller thread: window jobs hold windows of several lengths (set_window_mixed) */
     int done_ready;                /* atomic: the next job in flush order is finished (set under mu), so a
                                     * poll with nothing to complete takes no lock */
     uint64_t next_due;             /* caller thread: the oldest first-submission time of the open jobs
@@ -305,6 +320,7 @@ int pquic_fec_batch_unregister_heap(pquic_fec_batcher_t *b, void *base) {
 static void job_free(job_t *j) {
     if (!j) return;
     fecgpu_host_free(j->wrow);
+    free(j->wlen);
     free(j->rowsym);
     free(j->order);
     fecgpu_host_free(j->srow);
@@ -373,7 +389,8 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
     }
     /* gather tables (generate or recover with a registered heap; XOR where the engine has its row forms):
      * grown on reuse like the repair table */
-    j->gather = op == OP_SPAN ||  /* a span job runs on row tables whatever is registered */
+    const int mixed = op == OP_WINDOW && __atomic_load_n(&b->window_mixed, __ATOMIC_RELAXED);
+    j->gather = op == OP_SPAN || mixed ||  /* a span job and a mixed window job run on row tables whatever is registered */
                 ((op == OP_WINDOW ? window_rows_available() : !xor_scheme || xor_rows_available()) &&
                  __atomic_load_n(&b->nheaps, __ATOMIC_RELAXED) > 0);
     if (j->gather && RECOVERS(op) && j->pre_cap < (size_t)cap * k) {
@@ -428,6 +445,13 @@ static int job_prepare(pquic_fec_batcher_t *b, job_t *j, int op, int xor_scheme,
     }
     j->ragged = 0;
     j->ncopy = 0;
+    if (mixed) {  /* no staged form: the tables and the lengths, or no job */
+        if (!j->wlen) j->wlen = malloc(j->cap_alloc);
+        if (!j->gather || !j->wlen) return -1;
+    }
+    j->mixed = mixed;
+    j->wlo = UINT32_MAX;
+    j->whi = 0;
     if (op == OP_WINDOW) {  /* window tables: start rows (page-locked), the stream's symbols, the grouping */
         if (!j->wrow) j->wrow = fecgpu_host_alloc((size_t)cap * 4);
         if (!j->order) j->order = malloc((size_t)cap * 4);
@@ -566,6 +590,12 @@ static void run_engine(fecgpu_host_ctx_t *c, job_t *j) {
     if (j->op == OP_SPAN)
         j->rc = fecgpu_rlc_span_decode_rows_fused_host(c, j->srow, j->slen, j->rrow, j->rlen, j->blen, j->n, j->k, j->r,
                                                        S, j->seeds, j->roff, j->rnss, j->sp, j->rp, j->st, j->rec);
+    else if (j->op == OP_WINDOW && j->mixed && j->wlo == j->whi)  /* one length after all: the plain row form */
+        j->rc = fecgpu_rlc_window_encode_rows_host(c, j->srow, j->slen, j->nrows, j->wrow, j->rrow, j->blen, j->n, j->whi,
+                                                   j->r, S);
+    else if (j->op == OP_WINDOW && j->mixed)
+        j->rc = fecgpu_rlc_window_encode_rows_var_host(c, j->srow, j->slen, j->nrows, j->wrow, j->wlen, j->rrow,
+                                                       j->blen, j->n, j->k, j->r, S);
     else if (j->op == OP_WINDOW && j->gather)
         j->rc = fecgpu_rlc_window_encode_rows_host(c, j->srow, j->slen, j->nrows, j->wrow, j->rrow, j->blen, j->n, j->k,
                                                    j->r, S);
@@ -978,16 +1008,17 @@ static void stage_windows(pquic_fec_batcher_t *b, job_t *j) {
             run = nrows;
         }
         uint64_t start = nrows;
+        const uint32_t kw = j->mixed ? j->wlen[i] : k;  /* the window's own length; k bounds the look-back */
         const uint64_t lo = nrows - run > k ? nrows - k : run;
         for (uint64_t q = nrows; q-- > lo;) {  /* the newest row holding the window's first symbol */
             if (!ss[0] || j->rowsym[q] != ss[0]) continue;
             uint32_t x = 0;
-            while (x < k && q + x < nrows && ss[x] && j->rowsym[q + x] == ss[x]) x++;
-            if (q + x == nrows || x == k) start = q;  /* continues the run to its end, or lies within it */
+            while (x < kw && q + x < nrows && ss[x] && j->rowsym[q + x] == ss[x]) x++;
+            if (q + x == nrows || x == kw) start = q;  /* continues the run to its end, or lies within it */
             break;
         }
         j->wrow[i] = (uint32_t)start;
-        for (uint64_t x = nrows - start; x < k; x++) j->rowsym[nrows++] = ss[x];
+        for (uint64_t x = nrows - start; x < kw; x++) j->rowsym[nrows++] = ss[x];
     }
     j->nrows = nrows;
     if (j->gather) {
@@ -1225,6 +1256,7 @@ pquic_fec_batcher_t *pquic_fec_batcher_create(const pquic_fec_batch_cfg_t *cfg) 
     b->next_due = UINT64_MAX;
     b->pf = (uint32_t)env_int("PQUIC_FEC_BATCH_PREFETCH", 8, 0, 64);
     b->full_rank = env_int("PQUIC_FEC_BATCH_FULL_RANK", 0, 0, 1) && full_rank_available();
+    b->window_mixed = env_int("PQUIC_FEC_BATCH_WINDOW_MIXED", 0, 0, 1) && window_mixed_available();
     const size_t chunk = (size_t)cfg->batch_blocks * 20 * b->stride / (size_t)cfg->nstreams;
     b->nengines = env_int("PQUIC_FEC_BATCH_ENGINES", 2, 1, MAX_ENGINES);
     for (int e = 0; e < b->nengines; e++) {
@@ -1342,8 +1374,9 @@ static job_t *open_job(pquic_fec_batcher_t *b, int op, int xor_scheme, uint32_t 
     return j;
 }
 
+/* kq: the k of the queue's key when it is not the block's own (a mixed window job's class), else 0 */
 static int submit(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t *fb, int op, int xor_scheme,
-                  uint64_t now_us, pquic_fec_block_done_fn done, void *user) {
+                  uint32_t kq, uint64_t now_us, pquic_fec_block_done_fn done, void *user) {
     if (!b || !fb || !done) return -1;
     if (!g_fec_bound) {
         b->stats.immediate++;
@@ -1373,9 +1406,14 @@ static int submit(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t
     }
     if (maxl > b->cfg.max_symbol) return -1;
     int slot;
-    job_t *j = open_job(b, op, xor_scheme, k, r, &slot);
+    job_t *j = open_job(b, op, xor_scheme, kq ? kq : k, r, &slot);
     if (!j) return -1;
     const uint32_t i = j->n;
+    if (j->mixed) {
+        j->wlen[i] = (uint8_t)k;
+        if (k < j->wlo) j->wlo = k;
+        if (k > j->whi) j->whi = k;
+    }
     j->fbn[i] = fb->fec_block_number & 0xffffffu;  /* rows are copied later, by a stager */
     j->ent[i] = (entry_t){.cnx = cnx, .fb = fb, .done = done, .user = user, .maxl = maxl, .nalloc = -1};
     if (GENERATES(op))  /* the protocol operation's allocations, in its order, on this thread */
@@ -1396,7 +1434,7 @@ static int submit(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t
 
 int pquic_fec_batch_generate(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t *fb, int xor_scheme,
                              uint64_t now_us, pquic_fec_block_done_fn done, void *user) {
-    return submit(b, cnx, fb, OP_GENERATE, xor_scheme ? 1 : 0, now_us, done, user);
+    return submit(b, cnx, fb, OP_GENERATE, xor_scheme ? 1 : 0, 0, now_us, done, user);
 }
 
 int pquic_fec_batch_generate_window(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t *fb,
@@ -1404,15 +1442,18 @@ int pquic_fec_batch_generate_window(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx,
     /* window jobs need block number 0 (shared coefficients) and a stream the kernel's 32-bit offsets
      * reach; anything else is an ordinary block */
     if (!b || !fb) return -1;
-    const size_t worst = ((size_t)b->cfg.batch_blocks + 1) * fb->total_source_symbols * window_stride(b);
+    /* mixed mode: the queue's k is the class that holds the window, the smallest of 16, 32, 64 and 128 */
+    const uint32_t kw = fb->total_source_symbols;
+    const uint32_t kq = !b->window_mixed || !kw ? 0 : kw <= 16 ? 16 : kw <= 32 ? 32 : kw <= 64 ? 64 : 128;
+    const size_t worst = ((size_t)b->cfg.batch_blocks + 1) * (kq ? kq : kw) * window_stride(b);
     if (fb->fec_block_number != 0 || worst >= ((size_t)1 << 31))
-        return submit(b, cnx, fb, OP_GENERATE, 0, now_us, done, user);
-    return submit(b, cnx, fb, OP_WINDOW, 0, now_us, done, user);
+        return submit(b, cnx, fb, OP_GENERATE, 0, 0, now_us, done, user);
+    return submit(b, cnx, fb, OP_WINDOW, 0, kq, now_us, done, user);
 }
 
 int pquic_fec_batch_recover(pquic_fec_batcher_t *b, picoquic_cnx_t *cnx, pquic_fec_block_t *fb, int xor_scheme,
                             uint64_t now_us, pquic_fec_block_done_fn done, void *user) {
-    return submit(b, cnx, fb, OP_RECOVER, xor_scheme ? 1 : 0, now_us, done, user);
+    return submit(b, cnx, fb, OP_RECOVER, xor_scheme ? 1 : 0, 0, now_us, done, user);
 }
 
 /* The queue shapes of span jobs: K padded to 64 or 128 columns, R to 8, 32 or 128 slots. */
@@ -1720,6 +1761,16 @@ int pquic_fec_batch_set_full_rank(pquic_fec_batcher_t *b, int on) {
     if (!b || !full_rank_available()) return -1;
     if (b->stats.submitted != b->stats.completed) return -1;  /* a block is queued or in flight */
     b->full_rank = on != 0;
+    return 0;
+}
+
+int pquic_fec_batch_set_window_mixed(pquic_fec_batcher_t *b, int on) {
+    if (!b || !window_mixed_available()) return -1;
+    if (b->stats.submitted != b->stats.completed) return -1;  /* a block is queued or in flight */
+    /* an open queue is empty here; it goes back to the free list, so no job prepared for the other mode stays open */
+    for (int s = 0; s < MAX_OPEN; s++)
+        if (b->open[s]) flush_job(b, s, &b->stats.flushed_drain);
+    __atomic_store_n(&b->window_mixed, on != 0, __ATOMIC_RELAXED);
     return 0;
 }
 

@@ -26,6 +26,8 @@
 //   k_xor_encode_rows / k_xor_decode_rows   XOR on rows given by address, a length per row, in one pass.
 //   k_rlc_encode_sc / _sc_rows   window encode on shared coefficients, 2 KiB chunks of the windows x bytes
 //                  space; _sc_rows stores every repair to its row address for the window's own length.
+//   k_rlc_encode_sc_rows_var   _sc_rows over windows of their own number of symbols, sorted into classes of
+//                  one length whose chunks never mix lengths.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -3331,6 +3333,105 @@ static bool launch_encode_sc_rows(const uint8_t *sym, const uint32_t *wrow, cons
   return true;
 }
 
+// Windows of their own length (fecgpu_rlc_window_encode_rows_var_host): every window is block number 0, so
+// the coefficient of (position j, repair i) is the same in a window of 7 symbols and in one of 30, and the
+// rows built once per workgroup for kmax serve every length.  The host sorts the windows into classes of
+// one length (fecgpu_rlc_window_classes): perm[] maps a sorted position to its window, class x holds cnt[x]
+// windows of len[x] symbols from sorted position first[x], and its windows x bytes space is cut into 2 KiB
+// chunks of its own from chunk cchunk[x] on (cls = first[kmax], cnt[kmax], len[kmax], cchunk[kmax]; entries
+// past the last class hold cchunk = 2^32 - 1).  A chunk therefore never holds two lengths: the wave finds
+// its class (a compare per table entry, two ballots), and runs the body as generated with nsrc = k = the
+// class's length on the first rows of the coefficient table.  A piece past the end of its class reads row 0
+// of the stream and stores nothing; at most one chunk per class has such pieces.
+template <int RT>
+__global__ __launch_bounds__(64) void k_rlc_encode_sc_rows_var(const uint8_t *__restrict__ sym,
+                                                               const uint32_t *__restrict__ wrow,
+                                                               const uint64_t *__restrict__ rep_rows,
+                                                               const uint32_t *__restrict__ blk_len,
+                                                               const uint32_t *__restrict__ perm,
+                                                               const uint32_t *__restrict__ cls, uint64_t nch,
+                                                               int kmax, int r, int L, int cap, int r0) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  constexpr int CSB = FEC_BS_COEF_ROW_BYTES(RT);
+  const int lane = threadIdx.x;
+  const int rt = r - r0 < RT ? r - r0 : RT;
+  if (lane < RT) {  // coefficient rows of repairs r0 .. r0 + rt - 1 for kmax positions: as k_rlc_encode_sc
+    uint16_t *row0 = reinterpret_cast<uint16_t *>(lds);
+    uint16_t *row = row0 + FEC_BS_FIELD_SLOT(RT, lane);
+    if (lane < rt) {
+      Tmt t;
+      tmt_init(t, rlc_seed(0u, (uint32_t)(r0 + lane)));
+      for (int j = 0; j < kmax; j++) row[j * (CSB / 2)] = FEC_BS_FIELD(tmt_coef(t), lane);
+    } else {
+      for (int j = 0; j < kmax; j++) row[j * (CSB / 2)] = 0;
+    }
+    if constexpr (RT < 4) {
+      if (lane == 0)
+        for (int j = 0; j < kmax; j++)
+          for (int x = RT; x < 4; x++) row0[j * (CSB / 2) + FEC_BS_FIELD_SLOT(RT, x)] = 0;
+    }
+  }
+  __syncthreads();
+  const uint64_t sp = (uint64_t)(uintptr_t)sym;
+  for (uint64_t c = blockIdx.x; c < nch; c += gridDim.x) {
+    // the chunk's class: the last one that begins at or before it (cchunk ascends, cchunk[0] == 0)
+    const uint32_t *cch = cls + 3 * kmax;
+    const uint32_t c0 = lane < kmax ? cch[lane] : 0xffffffffu;
+    const uint32_t c1 = lane + 64 < kmax ? cch[lane + 64] : 0xffffffffu;
+    const int nle = __popcll(__ballot((uint64_t)c0 <= c)) + __popcll(__ballot((uint64_t)c1 <= c));
+    const int x = nle ? nle - 1 : 0;
+    const uint32_t first = __builtin_amdgcn_readfirstlane(cls[x]);
+    const uint32_t cnt = __builtin_amdgcn_readfirstlane(cls[kmax + x]);
+    const uint32_t k = __builtin_amdgcn_readfirstlane(cls[2 * kmax + x]);
+    const uint32_t cc = __builtin_amdgcn_readfirstlane(cch[x]);
+    const uint64_t F = (uint64_t)cnt * (uint64_t)L;  // the class's windows x bytes space
+    const uint64_t F0 = (c - cc) * 2048;
+    uint32_t off[2], tq[2], nb[2];
+    uint64_t tp[2], vm[2], vs[2];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const uint64_t p = F0 + 16u * (uint32_t)(lane + 64 * q);
+      const bool ok = p < F;
+      const uint64_t sw = ok ? p / (uint64_t)L : 0;
+      const uint32_t t = ok ? (uint32_t)(p - sw * (uint64_t)L) : 0u;
+      const uint64_t w = ok ? perm[first + sw] : 0;  // never a window of the next class
+      uint32_t bl = ok ? blk_len[w] : 0u;
+      if (bl > (uint32_t)cap) bl = (uint32_t)cap;
+      off[q] = ok ? wrow[w] * (uint32_t)L + t : 0u;
+      tq[q] = t;
+      nb[q] = bl > t ? (bl - t < 16u ? bl - t : 16u) : 0u;
+      tp[q] = (uint64_t)(uintptr_t)(rep_rows + w * (uint64_t)r + (uint64_t)r0);
+      vm[q] = __ballot(nb[q] == 16u);
+      vs[q] = __ballot(nb[q] != 0u && nb[q] < 16u);
+    }
+    if constexpr (RT == 1) BS_CALL_ENCSCL(1);
+    else if constexpr (RT == 2) BS_CALL_ENCSCL(2);
+    else if constexpr (RT == 4) BS_CALL_ENCSCL(4);
+    else BS_CALL_ENCSCL(8);
+  }
+}
+
+// launch_encode_sc_rows's limits, for kmax.  The caller has checked the class tables' shape (nch chunks).
+static bool launch_encode_sc_rows_var(const uint8_t *sym, const uint32_t *wrow, const uint64_t *rep_rows,
+                                      const uint32_t *blk_len, const uint32_t *perm, const uint32_t *cls,
+                                      uint64_t nch, uint64_t nrows, int kmax, int r, int L, int cap, hipStream_t s) {
+  if (!knob(K_WINDOW_SC) || L % 16 || (uintptr_t)sym % 16) return false;
+  if ((nrows + (uint64_t)kmax) * (uint64_t)L >= (1ull << 31)) return false;
+  const size_t lds = (size_t)kmax * FEC_BS_COEF_ROW_BYTES(8);
+  for (int r0 = 0; r0 < r; r0 += 8) {
+    const int rt = r - r0 < 8 ? r - r0 : 8;
+#define SC_ROWS_VAR_GO(RT)                                                                                      \
+  hipLaunchKernelGGL((k_rlc_encode_sc_rows_var<RT>), dim3(grid_for(nch)), dim3(64), lds, s, sym, wrow, rep_rows, \
+                     blk_len, perm, cls, nch, kmax, r, L, cap, r0)
+    if (rt >= 5) SC_ROWS_VAR_GO(8);
+    else if (rt >= 3) SC_ROWS_VAR_GO(4);
+    else if (rt == 2) SC_ROWS_VAR_GO(2);
+    else SC_ROWS_VAR_GO(1);
+#undef SC_ROWS_VAR_GO
+  }
+  return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // LDS-ring data path (bs2_* bodies, gen_bitslice.py body2): the sources of a group stream into a
 // per-wave LDS ring by LDS-DMA, D-1 rows ahead (up to 1 KiB per wave-instruction, linear in memory
@@ -4941,6 +5042,41 @@ int fecgpu_rlc_window_encode_rows(const uint64_t *rows, const uint32_t *row_len,
   if ((rc = launch_gather(rows, row_len, nrows, W, workspace, nullptr, nullptr, 1, s))) return rc;
   if (!launch_encode_sc_rows((const uint8_t *)workspace, wrow, rep_rows, blk_len, nrows, nwindows, (int)k, (int)r,
                              (int)W, (int)symbol_size, s))
+    return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: stream of 2 GiB or more, or window_sc knob 0");
+  HIPCHK(hipGetLastError());
+  count_encode(nwindows);
+  return FECGPU_OK;
+}
+
+// fecgpu_rlc_window_encode_rows for windows of their own length, sorted into classes by
+// fecgpu_rlc_window_classes (perm[nwindows], cls[4 * kmax] and its nchunks: device-accessible, trusted as
+// wrow is).  The gather pass is unchanged; the classes only steer the coding kernel.
+int fecgpu_rlc_window_encode_rows_var_internal(const uint64_t *rows, const uint32_t *row_len, uint64_t nrows,
+                                               const uint32_t *wrow, const uint64_t *rep_rows,
+                                               const uint32_t *blk_len, uint64_t nwindows, uint32_t kmax, uint32_t r,
+                                               uint32_t symbol_size, const uint32_t *perm, const uint32_t *cls,
+                                               uint64_t nchunks, void *workspace, size_t workspace_bytes,
+                                               void *stream) {
+  if (nwindows == 0) return FECGPU_OK;
+  if (!rows || !row_len || !wrow || !rep_rows || !blk_len || !perm || !cls)
+    return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: NULL table");
+  int rc = check_common(rows, rep_rows, nwindows, kmax, r, symbol_size);
+  if (rc) return rc;
+  if (r == 0) return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: r out of range [1,128]");
+  if (nchunks == 0 || nchunks >= 0xffffffffull)
+    return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: class chunks out of range");
+  if (!workspace || (uintptr_t)workspace % 16)
+    return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: workspace missing or not 16-byte aligned");
+  const uint32_t W = window_rows_width(symbol_size);
+  if (!knob(K_WINDOW_SC) || (nrows + (uint64_t)kmax) * (uint64_t)W >= (1ull << 31))
+    return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: stream of 2 GiB or more, or window_sc knob 0");
+  if (workspace_bytes < fecgpu_rlc_window_rows_workspace(nrows, symbol_size))
+    return set_err(FECGPU_ERR_NOMEM, "%s", "window rows workspace too small");
+  if (int rc2 = bs_table_check()) return rc2;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = launch_gather(rows, row_len, nrows, W, workspace, nullptr, nullptr, 1, s))) return rc;
+  if (!launch_encode_sc_rows_var((const uint8_t *)workspace, wrow, rep_rows, blk_len, perm, cls, nchunks, nrows,
+                                 (int)kmax, (int)r, (int)W, (int)symbol_size, s))
     return set_err(FECGPU_ERR_INVALID, "%s", "window rows encode: stream of 2 GiB or more, or window_sc knob 0");
   HIPCHK(hipGetLastError());
   count_encode(nwindows);

@@ -38,6 +38,12 @@ FECGPU_INTERNAL int fecgpu_rlc_decode_rows_fused_internal(
     const uint32_t *blk_len, uint64_t nblocks, uint32_t k, uint32_t r, uint32_t symbol_size, const uint32_t *rep_seed,
     const uint64_t *src_present, const uint64_t *rep_present, uint8_t *status, uint64_t *recovered, void *workspace,
     size_t workspace_bytes, void *stream, int full);
+// fec_engine.hip: fecgpu_rlc_window_encode_rows on windows of their own length, sorted into classes by
+// fecgpu_rlc_window_classes: perm[nwindows], cls[4 * kmax] and nchunks are its outputs, device-accessible
+FECGPU_INTERNAL int fecgpu_rlc_window_encode_rows_var_internal(
+    const uint64_t *rows, const uint32_t *row_len, uint64_t nrows, const uint32_t *wrow, const uint64_t *rep_rows,
+    const uint32_t *blk_len, uint64_t nwindows, uint32_t kmax, uint32_t r, uint32_t symbol_size, const uint32_t *perm,
+    const uint32_t *cls, uint64_t nchunks, void *workspace, size_t workspace_bytes, void *stream);
 // fec_engine.hip: fecgpu_rlc_encode_rows_len with the packed arrays given one by one
 FECGPU_INTERNAL int fecgpu_rlc_encode_rows_len_internal(const uint64_t *src_rows, const uint32_t *src_len,
                                                         const uint64_t *rep_rows, const uint32_t *blk_len,

@@ -48,6 +48,8 @@ struct fecgpu_host_ctx {
   size_t chunk_bytes = 64u << 20;
   Slot slot[kMaxStreams];
   hipEvent_t yev[16] = {};  // the Pacer's slice completions (created on first use)
+  uint32_t *h_sort = nullptr;  // page-locked: the sorted windows of fecgpu_rlc_window_encode_rows_var_host
+  size_t cap_sort = 0;
   std::mutex mu;
 };
 
@@ -88,6 +90,7 @@ void fecgpu_host_ctx_destroy(fecgpu_host_ctx_t *c) {
   }
   for (hipEvent_t e : c->yev)
     if (e) (void)hipEventDestroy(e);
+  fecgpu_host_free(c->h_sort);
   delete c;
 }
 
@@ -758,6 +761,10 @@ int fecgpu_rlc_encode_rows_fused_host(fecgpu_host_ctx_t *c, const uint64_t *src_
 // ---- window jobs on rows (fecgpu_rlc_window_encode_rows_host) ----
 // Unsliced: one gathered stream in slot 0's d_src serves all the windows.  The five tables have two
 // entry counts (stream rows, windows), so each goes to stage_tables as one block of its whole size.
+static int window_rows_run(fecgpu_host_ctx_t *c, const uint64_t *rows, const uint32_t *row_len, uint64_t nrows,
+                           const uint32_t *wrow, const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nwin,
+                           uint32_t k, uint32_t r, uint32_t L);
+
 int fecgpu_rlc_window_encode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *rows, const uint32_t *row_len,
                                        uint64_t nrows, const uint32_t *wrow, const uint64_t *rep_rows,
                                        const uint32_t *blk_len, uint64_t nwin, uint32_t k, uint32_t r, uint32_t L) {
@@ -772,6 +779,13 @@ int fecgpu_rlc_window_encode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *row
     if (row_len[x] > L) return rows_len_invalid("row_len above symbol_size");
   if (!c) return rows_len_invalid("NULL host context");
   if (!nwin) return FECGPU_OK;
+  return window_rows_run(c, rows, row_len, nrows, wrow, rep_rows, blk_len, nwin, k, r, L);
+}
+
+// the call above after its checks (also the variable-length form's, when every window is k long)
+static int window_rows_run(fecgpu_host_ctx_t *c, const uint64_t *rows, const uint32_t *row_len, uint64_t nrows,
+                           const uint32_t *wrow, const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nwin,
+                           uint32_t k, uint32_t r, uint32_t L) {
   const size_t W = (L + 15u) & ~(size_t)15;
   if (!fecgpu_knob_window_sc() || (nrows + (uint64_t)k) * W >= (1ull << 31)) {
     // the windows as blocks of their own, every block number 0; a row counts for min(row_len, blk_len[w])
@@ -799,6 +813,75 @@ int fecgpu_rlc_window_encode_rows_host(fecgpu_host_ctx_t *c, const uint64_t *row
     rc = fecgpu_rlc_window_encode_rows(t[ROWS].at<const uint64_t>(0), t[RLEN].at<const uint32_t>(0), nrows,
                                        t[WROW].at<const uint32_t>(0), t[REP].at<const uint64_t>(0),
                                        t[BLEN].at<const uint32_t>(0), nwin, k, r, L, s.d_src, s.cap_src, s.st);
+  } while (0);
+  return finish(c, rc);
+}
+
+// Windows of their own length: sorted into classes of one length (fecgpu_rlc_window_classes, window_classes.c),
+// perm and the class table staged with the caller's tables.  Equal lengths: the call above, unchanged.
+int fecgpu_rlc_window_encode_rows_var_host(fecgpu_host_ctx_t *c, const uint64_t *rows, const uint32_t *row_len,
+                                           uint64_t nrows, const uint32_t *wrow, const uint8_t *wlen,
+                                           const uint64_t *rep_rows, const uint32_t *blk_len, uint64_t nwin,
+                                           uint32_t kmax, uint32_t r, uint32_t L) {
+  if (!rows || !row_len || !wrow || !wlen || !rep_rows || !blk_len)
+    return rows_len_invalid("NULL row / length / window table");
+  if (int rc = rows_len_shape(kmax, r, L)) return rc;
+  if (r == 0) return rows_len_invalid("r out of range [1,128]");
+  bool equal = true;
+  for (uint64_t w = 0; w < nwin; w++) {
+    if (wlen[w] < 1 || wlen[w] > kmax) return rows_len_invalid("window length: wlen out of range [1,kmax]");
+    if ((uint64_t)wrow[w] + wlen[w] > nrows) return rows_len_invalid("window past the stream: wrow + wlen above nrows");
+    if (blk_len[w] > L) return rows_len_invalid("blk_len above symbol_size");
+    equal = equal && wlen[w] == kmax;
+  }
+  for (uint64_t x = 0; x < nrows; x++)
+    if (row_len[x] > L) return rows_len_invalid("row_len above symbol_size");
+  if (!c) return rows_len_invalid("NULL host context");
+  if (!nwin) return FECGPU_OK;
+  if (equal) return window_rows_run(c, rows, row_len, nrows, wrow, rep_rows, blk_len, nwin, kmax, r, L);
+  const size_t W = (L + 15u) & ~(size_t)15;
+  if (!fecgpu_knob_window_sc() || (nrows + (uint64_t)kmax) * W >= (1ull << 31)) {
+    // the windows as blocks of kmax rows, every block number 0; a position past the window's length is a row
+    // of 0 bytes at address 0, never dereferenced: its coefficient multiplies nothing
+    std::vector<uint64_t> src(nwin * (size_t)kmax, 0);
+    std::vector<uint32_t> len(nwin * (size_t)kmax, 0u), zero_fbn(nwin, 0u);
+    for (uint64_t w = 0; w < nwin; w++)
+      for (uint32_t j = 0; j < wlen[w]; j++) {
+        src[w * kmax + j] = rows[wrow[w] + j];
+        len[w * kmax + j] = std::min(row_len[wrow[w] + j], blk_len[w]);
+      }
+    return fecgpu_rlc_encode_rows_fused_host(c, src.data(), len.data(), rep_rows, blk_len, nwin, kmax, r, L,
+                                             zero_fbn.data());
+  }
+  // perm[nwin] and cls[4 * kmax] in one array of the context's own page-locked memory (grown, never shrunk):
+  // with the caller's tables page-locked all stay in place, else stage_tables copies it with them
+  std::lock_guard<std::mutex> g(c->mu);
+  HCHK(hipSetDevice(c->device));
+  const size_t tabs = (nwin + 4 * (size_t)kmax) * sizeof(uint32_t);
+  if (tabs > c->cap_sort) {
+    fecgpu_host_free(c->h_sort);
+    c->cap_sort = 0;
+    if (!(c->h_sort = (uint32_t *)fecgpu_host_alloc(tabs + tabs / 2))) return FECGPU_ERR_HIP;
+    c->cap_sort = tabs + tabs / 2;
+  }
+  uint32_t *perm = c->h_sort, ncls = 0;
+  uint64_t nch = 0;
+  int rc = fecgpu_rlc_window_classes(wlen, nwin, kmax, L, perm, perm + nwin, &ncls, &nch);
+  if (rc) return rc;
+  enum { ROWS, RLEN, WROW, REP, BLEN, SORT };
+  Table t[] = {in(rows, nrows * 8), in(row_len, nrows * 4), in(wrow, nwin * 4), in(rep_rows, nwin * r * 8),
+               in(blk_len, nwin * 4), in(perm, tabs)};
+  bool in_place;
+  rc = stage_tables(c, t, 1, &in_place);
+  Slot &s = c->slot[0];  // the stream that carries the copies of staged tables
+  do {
+    if (rc) break;
+    const size_t need = fecgpu_rlc_window_rows_workspace(nrows, L);
+    LCHK(grow(&s.d_src, &s.cap_src, need));
+    rc = fecgpu_rlc_window_encode_rows_var_internal(
+        t[ROWS].at<const uint64_t>(0), t[RLEN].at<const uint32_t>(0), nrows, t[WROW].at<const uint32_t>(0),
+        t[REP].at<const uint64_t>(0), t[BLEN].at<const uint32_t>(0), nwin, kmax, r, L, t[SORT].at<const uint32_t>(0),
+        t[SORT].at<const uint32_t>(0) + nwin, nch, s.d_src, s.cap_src, s.st);
   } while (0);
   return finish(c, rc);
 }

@@ -132,6 +132,9 @@ def load_library(path: str = LIB_PATH, private: bool = False):
         L.fecgpu_rlc_window_rows_workspace.restype = sz
         L.fecgpu_rlc_window_encode_rows.argtypes = [v, v, u64, v, v, v, u64, u32, u32, u32, v, sz, v]
         L.fecgpu_rlc_window_encode_rows_host.argtypes = [v, v, v, u64, v, v, v, u64, u32, u32, u32]
+    if hasattr(L, "fecgpu_rlc_window_encode_rows_var_host"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
+        L.fecgpu_rlc_window_encode_rows_var_host.argtypes = [v, v, v, u64, v, v, v, v, u64, u32, u32, u32]
+        L.fecgpu_rlc_window_classes.argtypes = [v, u64, u32, u32, v, v, C.POINTER(u32), C.POINTER(u64)]
     if hasattr(L, "fecgpu_block_svc_rlc_encode_rows"):  # an older build (PQUIC_AMD_LIB, A/B baselines) lacks these
         L.fecgpu_block_svc_rlc_encode_rows.argtypes = [v, v, v, v, u32, u32, u32, u32]
         L.fecgpu_block_svc_rlc_decode_rows.argtypes = [v, v, v, v, v, u32, u32, u32, v, v, v, C.c_int, v, v]
@@ -182,6 +185,28 @@ def span_layout(first_id, nss):
     if rc != OK:
         raise FecGpuError(f"fecgpu_rlc_span_layout failed ({rc}): {L.fecgpu_last_error().decode()}")
     return base.value, K.value, off[:len(ids)]
+
+
+def window_classes(wlen, kmax: int, symbol_size: int):
+    """fecgpu_rlc_window_classes (host only): the windows' lengths (1..kmax) -> (perm, first, cnt, len, cchunk,
+    nchunks), a stable counting sort by length and the classes' tables cut to the classes present (numpy u32):
+    class x holds cnt[x] windows of len[x] symbols from sorted position first[x], its 2 KiB chunks begin at
+    chunk cchunk[x]; nchunks is their total.  Raises FecGpuError for a length outside 1..kmax or kmax outside
+    1..128."""
+    import numpy as np
+    L = load_library()
+    n = np.ascontiguousarray(wlen, dtype=np.uint8)
+    if n.ndim != 1:
+        raise ValueError("window_classes: wlen must be one-dimensional")
+    perm = np.zeros(max(len(n), 1), np.uint32)
+    cls = np.zeros(4 * max(min(int(kmax), 128), 1), np.uint32)
+    nc, nch = C.c_uint32(0), C.c_uint64(0)
+    rc = L.fecgpu_rlc_window_classes(n.ctypes.data, len(n), kmax, symbol_size, perm.ctypes.data, cls.ctypes.data,
+                                     C.byref(nc), C.byref(nch))
+    if rc != OK:
+        raise FecGpuError(f"fecgpu_rlc_window_classes failed ({rc}): {L.fecgpu_last_error().decode()}")
+    t = cls.reshape(4, -1)[:, :nc.value]
+    return perm[:len(n)], t[0].copy(), t[1].copy(), t[2].copy(), t[3].copy(), nch.value
 
 
 def span_one_launch_calls(lib=None) -> int:
@@ -709,3 +734,11 @@ class HostPath:
                                                               _addr(wrow), _addr(rep_rows), _addr(blk_len),
                                                               nwindows, k, r, L),
                   "fecgpu_rlc_window_encode_rows_host")
+
+    def rlc_window_encode_rows_var(self, rows, row_len, nrows, wrow, wlen, rep_rows, blk_len, nwindows, kmax, r, L):
+        """fecgpu_rlc_window_encode_rows_var_host: rlc_window_encode_rows with a length per window (wlen: host
+        u8, 1..kmax); window w protects rows wrow[w] .. wrow[w] + wlen[w] - 1."""
+        self._chk(self.lib.fecgpu_rlc_window_encode_rows_var_host(self.ctx, _addr(rows), _addr(row_len), nrows,
+                                                                  _addr(wrow), _addr(wlen), _addr(rep_rows),
+                                                                  _addr(blk_len), nwindows, kmax, r, L),
+                  "fecgpu_rlc_window_encode_rows_var_host")

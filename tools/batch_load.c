@@ -697,6 +697,17 @@ static int run_sender(int device, int k, int r, int L, int nconn, long nblocks, 
  * bl_set_ragged the batcher is opened for max_symbol bytes and every symbol's length is drawn as in the
  * ragged block legs (symbol q of a connection is packet q % k of pool block q / k); out[0] and out[7]
  * then count the bytes the symbols hold. */
+/* bl_set_window_walk(1, seed): the window sender protects what is in flight -- every connection's window
+ * length walks in 1..k by steps of -3..+3 per send (the same walks for one seed), the window is the last
+ * `length` symbols sent, and it asks for min(r, length) repairs (window_framework_sender.h:209-260).  out[7]
+ * then counts the windows' own symbols.  Default 0: every window k symbols. */
+static int g_walk;
+static uint64_t g_walk_seed;
+void bl_set_window_walk(int on, unsigned seed) {
+    g_walk = on != 0;
+    g_walk_seed = seed;
+}
+
 static int run_window(int device, int k, int r, int L, int step, int nconn, long nwindows, unsigned batch_blocks,
                       unsigned max_delay_us, int nstreams, int window_api, int register_heap, double out[8]) {
     if (k < 1 || k > 64 || r < 1 || step < 1 || nconn < 1 || L < 1 || L > 2048) return -1;
@@ -725,11 +736,13 @@ static int run_window(int device, int k, int r, int L, int step, int nconn, long
     g_lat = malloc(sizeof *g_lat * (size_t)(nwindows + nwindows / 5 + 1));
     g_nlat = 0;
     picoquic_cnx_t *cnx = calloc(nconn, sizeof *cnx);
-    if (!slots || !rings || !sent || !g_lat || !cnx) return -1;
-    uint64_t x = 0x5EEDF3C0;
+    int *wl = calloc(nconn, sizeof *wl);  /* bl_set_window_walk: each connection's window length */
+    if (!slots || !rings || !sent || !g_lat || !cnx || !wl) return -1;
+    uint64_t x = 0x5EEDF3C0, xw = g_walk_seed * 0x9E3779B97F4A7C15ull + 0x2545F4914F6CDD1Dull;
     for (size_t o = 0; o < pool_bytes; o++) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; pool[o] = (uint8_t)x; }
     for (int c = 0; c < nconn; c++) {
         cnx[c].id = c;
+        wl[c] = g_walk ? 1 + (c * 7) % k : k;
         sent[c] = k > step ? k - step : 0;  /* symbols already sent: the first window then ends at k */
     }
     pthread_once(&g_tsc_once, tsc_init);
@@ -762,12 +775,18 @@ static int run_window(int device, int k, int r, int L, int step, int nconn, long
             }
             sent[c] += step;
             memset(&s->fb, 0, sizeof s->fb);
-            for (int j = 0; j < k; j++) {
-                s->fb.source_symbols[j] = &rc[(sent[c] - k + j) % ring];
-                if (ragged) win_bytes += s->fb.source_symbols[j]->data_length;
+            if (g_walk) {
+                xw ^= xw << 13; xw ^= xw >> 7; xw ^= xw << 17;
+                wl[c] += (int)(xw % 7) - 3;
+                wl[c] = wl[c] < 1 ? 1 : wl[c] > k ? k : wl[c];
             }
-            s->fb.current_source_symbols = s->fb.total_source_symbols = (uint8_t)k;
-            s->fb.total_repair_symbols = (uint8_t)r;
+            const int kw = wl[c];
+            for (int j = 0; j < kw; j++) {
+                s->fb.source_symbols[j] = &rc[(sent[c] - kw + j) % ring];
+                if (ragged || g_walk) win_bytes += s->fb.source_symbols[j]->data_length;
+            }
+            s->fb.current_source_symbols = s->fb.total_source_symbols = (uint8_t)kw;
+            s->fb.total_repair_symbols = (uint8_t)(r < kw ? r : kw);
             s->busy = 1;
             s->cnx = NULL;  /* the repairs come from the thread arena */
             s->tally = &g_tally;
@@ -791,10 +810,10 @@ static int run_window(int device, int k, int r, int L, int step, int nconn, long
     out[4] = (double)(st.batches - st0.batches);
     out[5] = wall;
     out[6] = (double)(st.completed - st0.completed);
-    out[7] = (ragged ? (double)win_bytes : (double)nwindows * k * L) / wall / 1073741824.0;
+    out[7] = (ragged || g_walk ? (double)win_bytes : (double)nwindows * k * L) / wall / 1073741824.0;
     g_rows[0] = (double)(st.rows_in_place - st0.rows_in_place);
     g_rows[1] = (double)(st.rows_staged - st0.rows_staged);
-    free(slots); free(rings); free(sent); free(g_lat); free(cnx);
+    free(slots); free(rings); free(sent); free(g_lat); free(cnx); free(wl);
     g_lat = NULL;
     if (pinned) sched_setaffinity(0, sizeof saved, &saved);
     arena_unmap(&g_thread_arena);

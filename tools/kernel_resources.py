@@ -21,7 +21,7 @@ cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c"
        "-Rpass-analysis=kernel-resource-usage"] + EXTRA
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 want = re.compile(r"k_rlc_(encode_bs2?|recover_bs2?|recover_rows_fused|encode_rows|encode_sp|decode_small|"
-                  r"span_decode_small)<(\d+), (\d+|true|false)>")
+                  r"span_decode_small)<(\d+), (\d+|true|false)>|k_rlc_encode_sc(_rows|_rows_var)?<\d+>")
 rec, cur = {}, None
 for ln in out.splitlines():
     m = re.search(r"Function Name: (\S+)", ln)
